@@ -8,15 +8,21 @@ transitions for every resident chain, so the driver's `--steps 20` is SURVEY 8(d
 untimed steps are taken on throw-away chains, the chains are initialised again, and exactly K steps
 (one launch of the NUTS kernel, one trace of K * draws-per-step rows) are timed between
 barrier + synchronize pairs. value = useful leapfrogs (sum of n_steps, tree.ex:1612) per second
-over all GPUs; ESS/s (adaptation + sampling + the ESS kernel + the gather), the roofline of the
-NUTS kernel and the CPU checker's numbers ride along. Order of the default run: the eight_schools
+over all GPUs. A plain run does only that (set-up, adaptation, warmup, the K timed steps, the line).
+
+--full adds everything else: ESS/s (adaptation + sampling + the ESS kernel + the gather), the roofline
+of the NUTS kernel and the CPU checker's numbers ride along. Order of the --full run: the eight_schools
 sampling leg, the sv sampling leg (BASELINE.json's metric names both), then -- after every sampling leg
 -- the batched-leapfrog roofline leg and the CPU checker's legs (profiles/r4_driver_cmd/README.md says
-why the order matters). Split R-hat is computed on two independent routes that must agree to 1e-9,
+why the order matters). The legs that ride along keep the 1000-draw protocol whatever --steps
+(PROTOCOL_DRAWS). Split R-hat is computed on two independent routes that must agree to 1e-9,
 or every rank exits with code 3 (finish_model).
 
-    python bench.py --gpus N --steps K --warmup W      (N > 1 without a launcher: spawns the ranks)
+--dump-outputs DIR writes what the timed launch returned for its last step (dump_outputs).
+
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    (N > 1 without a launcher: spawns the ranks)
 """
 import argparse
 import ctypes as C
@@ -243,6 +249,97 @@ def reference_published(model):
                 comparable="no: different hardware, one chain, and not the implementation cpu_baseline times")
 
 
+def headline(*, model, d, K, W, B, adapt, Cper, world, dist, dev, leap_local, div_local, elapsed_local, epsilon,
+             lanes, warm_lanes, dense_mass=False):
+    """The line's headline fields: the max of the ranks' clocks and the sum of their counters (the same
+    collective calls on every rank) and what follows from those alone. Returns (line, elapsed s)."""
+    S = K * B
+    Ctot = Cper * world
+    stats = torch.tensor([elapsed_local, float(leap_local), float(div_local)], dtype=torch.float64, device=dev)
+    if dist is not None:
+        mx = stats.clone()
+        dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+        sm = stats.clone()
+        dist.all_reduce(sm, op=dist.ReduceOp.SUM)
+        elapsed, leapfrogs, divs = float(mx[0]), float(sm[1]), float(sm[2])
+    else:
+        elapsed, leapfrogs, divs = float(elapsed_local), float(leap_local), float(div_local)
+    out = {
+        "metric": "leapfrog_steps_per_s",
+        "value": leapfrogs / elapsed,
+        "unit": "leapfrog_steps/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": elapsed * 1e3 / K,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "%s d=%d, %d chains/GPU (%d total), %d draws/chain (%d steps of %d "
+                               "draws) after one shared %d-iteration warmup, max_tree_depth 10, "
+                               "target_accept 0.8%s"
+                               % (model, d, Cper, Ctot, S, K, B, adapt,
+                                  ", dense mass matrix" if dense_mass else ""),
+                   "draws_per_step": B, "draws_per_chain": S,
+                   "lanes_per_chain": lanes, "warmup_lanes_per_chain": warm_lanes, "seed": 42},
+        "divergent_transitions": divs,
+        "mean_leapfrogs_per_draw": leapfrogs / (S * Ctot),
+        "step_size": epsilon,
+    }
+    return out, elapsed
+
+
+DUMP_BYTES = 64 * 10 ** 6
+# the 1000-draw protocol of SURVEY 8(d): the legs that ride along under --full (sv, logistic, radon and the CPU
+# checker's) take at most this many draws per chain whatever --steps, so --full stays bounded in time and memory
+PROTOCOL_DRAWS = 1000
+# exmc_hip_ess_bulk ranks each series in LDS: 160 KB of doubles (exmc_hip.hip), EXMC_ERR_UNSUPPORTED beyond
+ESS_BULK_MAX_DRAWS = 20480
+
+
+def bulk_ess(comp, draws, S, d, Cper):
+    """Diagnostics.ess_bulk (diagnostics.ex:60-72) by the library's kernels: rank-normalise
+    (rank_scores_kernel) into a second trace, then the same ESS kernels on it -- BASELINE.md section 2 asks
+    for ESS/s by both. Returns ([d][Cper] per-chain bulk ESS, wall s), or (None, None) for series longer
+    than the rank kernel holds."""
+    if S > ESS_BULK_MAX_DRAWS:
+        return None, None
+    essb = torch.empty((d, Cper), dtype=torch.float64, device=draws.device)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    comp.check(comp.L.exmc_hip_ess_bulk(comp.h, draws.data_ptr(), S, d, Cper, essb.data_ptr()))
+    return essb, time.perf_counter() - t0
+
+
+def note_bulk_skipped(out, S):
+    out["ess_bulk_min_total"] = out["ess_bulk_per_s"] = None
+    out["ess_bulk_note"] = ("not computed: %d draws per chain, the library's bulk-ESS rank kernel holds at most %d"
+                            % (S, ESS_BULK_MAX_DRAWS))
+
+
+def dump_outputs(path, arrays, rank=0, world=1, chain_lo=0):
+    """--dump-outputs: what the timed launch handed back for its last step, one float64 .npy per array
+    (the chain axis last, as the library writes it). At most DUMP_BYTES over all ranks: where the chains do
+    not fit, a sample drawn with a fixed seed (the same chains on every run of the same arguments) is
+    written, and chain_index.npy says which chains. With more than one rank every rank writes its own
+    shard, the files named <name>.rank<r>.npy."""
+    arrays = {k: np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[-1]
+    per_chain = 8 + sum(a[..., 0].size * 8 for a in arrays.values())      # the chain_index entry included
+    keep = max(1, DUMP_BYTES // world // per_chain)
+    idx = np.arange(n)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[..., idx] for k, a in arrays.items()}
+    arrays["chain_index"] = (chain_lo + idx).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else ".rank%d" % rank
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def finish_model(*, model, d, K, W, B, adapt, Cper, world, rank, dist, draws, ess, leap_local, div_local,
                  elapsed_local, kernel_ms, adapt_s, ess_s, ess_ms, epsilon, lanes, warm_lanes,
                  bytes_per_leapfrog, gather_traces, rhat_fn, dense_mass=False, sync=lambda: None,
@@ -265,18 +362,11 @@ def finish_model(*, model, d, K, W, B, adapt, Cper, world, rank, dist, draws, es
     tests/test_gpu_rccl_one_rank.py: the RCCL calls executed on the real device of a one-GPU box; the
     line must equal the dist=None line). ess_bulk: [d][Cper] rank-normalised bulk ESS
     (diagnostics.ex:60-72) with its wall clock, or None."""
-    S = K * B
-    Ctot = Cper * world
     dev = draws.device
-    stats = torch.tensor([elapsed_local, float(leap_local), float(div_local)], dtype=torch.float64, device=dev)
-    if dist is not None:
-        mx = stats.clone()
-        dist.all_reduce(mx, op=dist.ReduceOp.MAX)
-        sm = stats.clone()
-        dist.all_reduce(sm, op=dist.ReduceOp.SUM)
-        elapsed, leapfrogs, divs = float(mx[0]), float(sm[1]), float(sm[2])
-    else:
-        elapsed, leapfrogs, divs = float(elapsed_local), float(leap_local), float(div_local)
+    out, elapsed = headline(model=model, d=d, K=K, W=W, B=B, adapt=adapt, Cper=Cper, world=world,
+                                       dist=dist, dev=dev, leap_local=leap_local, div_local=div_local,
+                                       elapsed_local=elapsed_local, epsilon=epsilon, lanes=lanes,
+                                       warm_lanes=warm_lanes, dense_mass=dense_mass)
 
     ess_sum = ess.sum(dim=1)
     # the sufficient-statistics route is always timed (it is what R-hat needs); sv also runs the
@@ -334,31 +424,11 @@ def finish_model(*, model, d, K, W, B, adapt, Cper, world, rank, dist, draws, es
                float((again_lib - again_stats).abs().max())))
     ess_min = float(ess_sum.min())
     total_s = adapt_s + elapsed + ess_s + gather_s
-    value = leapfrogs / elapsed
     if rank != 0:
         return None, ok
     local_lf = float(leap_local)
     achieved = bytes_per_leapfrog * local_lf / (kernel_ms * 1e-3) / 1e9
-    out = {
-        "metric": "leapfrog_steps_per_s",
-        "value": value,
-        "unit": "leapfrog_steps/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": elapsed * 1e3 / K,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "%s d=%d, %d chains/GPU (%d total), %d draws/chain (%d steps of %d "
-                               "draws) after one shared %d-iteration warmup, max_tree_depth 10, "
-                               "target_accept 0.8%s"
-                               % (model, d, Cper, Ctot, S, K, B, adapt,
-                                  ", dense mass matrix" if dense_mass else ""),
-                   "draws_per_step": B, "draws_per_chain": S,
-                   "lanes_per_chain": lanes, "warmup_lanes_per_chain": warm_lanes, "seed": 42},
+    out.update({
         "ess_per_s": ess_min / total_s,
         "ess_min_total": ess_min,
         "ess_wall_s": {"adaptation": adapt_s, "sampling": elapsed, "ess_kernel": ess_s,
@@ -373,9 +443,6 @@ def finish_model(*, model, d, K, W, B, adapt, Cper, world, rank, dist, draws, es
         "rhat_max_from_chain_stats": float(rhat_stats.max()),
         "rhat_routes_agree": ok,
         "rhat_routes_max_gap": float(gap.max()),
-        "divergent_transitions": divs,
-        "mean_leapfrogs_per_draw": leapfrogs / (S * Ctot),
-        "step_size": epsilon,
         "ess_kernel_ms": ess_ms,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
@@ -383,7 +450,7 @@ def finish_model(*, model, d, K, W, B, adapt, Cper, world, rank, dist, draws, es
                      "kernel": "nuts_kernel", "launches": 1, "kernel_ms": kernel_ms,
                      "algorithmic_bytes_per_leapfrog": bytes_per_leapfrog,
                      "leapfrogs_per_launch": local_lf},
-    }
+    })
     if ess_bulk_sum is not None:
         # Diagnostics.ess_bulk (diagnostics.ex:60-72): the same minimum over parameters on the
         # rank-normalised traces, with ITS kernels' wall clock in place of the Geyer kernel's
@@ -491,19 +558,28 @@ def main():
                     help="lanes per chain of the shared one-chain warmup (default: --lanes if given, else the "
                          "library's choice for the model)")
     ap.add_argument("--adapt", type=int, default=1000, help="NUTS adaptation iterations")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline figure: ESS/s and split R-hat by both "
+                         "routes, the rooflines, the sv / logistic / radon legs of the eight_schools line, the "
+                         "batched-leapfrog leg and the CPU checker's legs, which take at most the 1000-draw protocol "
+                         "(the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed launch returned for its last step (draws "
+                         "[B][d][C], n_steps, tree_depth, divergent, accept_prob [B][C]) as DIR/<name>.npy in float64, "
+                         "at most 64 MB in all (a seeded sample of the chains where more; chain_index.npy says which)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full only: skip the CPU checker's legs")
     ap.add_argument("--dense-mass", action="store_true",
                     help="opts[:dense_mass]: dense adaptation windows and a dense mass matrix while sampling "
                          "(layouts that carry it; not the default protocol, the CPU leg is skipped)")
     ap.add_argument("--no-multi-step", action="store_true",
-                    help="skip the batched-leapfrog roofline leg (development builds without that layout)")
+                    help="--full only: skip the batched-leapfrog roofline leg (development builds without that layout)")
     ap.add_argument("--gather-traces", action="store_true",
                     help="all-gather the full [S][d][C] traces for split R-hat instead of the "
                          "per-chain half-chain statistics (sv does by default: BASELINE.json's config)")
     ap.add_argument("--no-sv-leg", action="store_true",
-                    help="default run only: skip the sv(d=102) leg that rides on the eight_schools line")
+                    help="--full only: skip the sv(d=102) leg that rides on the eight_schools line")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="default run only: skip the logistic and radon legs (BASELINE configs 3 and 5)")
+                    help="--full only: skip the logistic and radon legs (BASELINE configs 3 and 5)")
     ap.add_argument("--independent-warmup", action="store_true",
                     help="sample_chains(ir, n, vectorized: false), sampler.ex:1139-1176: every chain runs its OWN "
                          "adaptation and then its draws, all chains in one launch (exmc_hip_sample_independent); "
@@ -562,7 +638,8 @@ def main():
         torch.cuda.synchronize()
 
     out, ok = run_model(args, args.model, rank, local_rank, world, dev, dist, barrier, primary=True)
-    if args.model == "eight_schools" and not args.no_sv_leg and not args.dense_mass:
+    extra_legs = args.full and args.model == "eight_schools" and not args.dense_mass
+    if extra_legs and not args.no_sv_leg:
         # BASELINE.json's metric names two models: the line the driver records carries the sv(d=102)
         # leg too -- 2048 chains per GPU (16384 over 8), the same 1000-draw protocol, the finished
         # traces all-gathered over RCCL as the config says, its CPU leg on a smaller sample
@@ -570,7 +647,7 @@ def main():
         ok = ok and ok_sv
         if rank == 0:
             out["models"] = {"sv": sv}
-    if args.model == "eight_schools" and not args.no_extra_legs and not args.dense_mass:
+    if extra_legs and not args.no_extra_legs:
         # BASELINE configs 3 and 5 in the same record: logistic 8192 and radon 1024 chains per GPU (their
         # GPU legs are a few hundred milliseconds each; their CPU legs are bounded to a few seconds)
         for extra in ("logistic", "radon"):
@@ -610,6 +687,8 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
     B = args.draws_per_step
     if K < 1 or B < 1 or W < 0:
         raise SystemExit("--steps and --draws-per-step must be >= 1, --warmup >= 0")
+    if not primary:
+        K = min(K, max(1, PROTOCOL_DRAWS // B))
     S = K * B                      # draws per chain in the timed region
     Cper = (args.chains_per_gpu if primary else 0) or DEFAULT_CHAINS_PER_GPU[model]
     Ctot = Cper * world
@@ -625,7 +704,7 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
 
     if getattr(args, "independent_warmup", False):
         return run_model_independent(args, model, spec, comp, opts, lanes, bytes_per_leapfrog, gather_traces,
-                                     rank, world, dev, dist, barrier, Cper)
+                                     rank, world, dev, dist, barrier, Cper, primary)
     # --- shared adaptation warmup: every rank runs it with the same seed (deterministic, so no
     # broadcast is needed) ---
     # (a 2-iteration throwaway call first, untimed like the W warmup steps of the sampling region:
@@ -670,6 +749,18 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = comp.last_kernel_ms                   # HIP events on the library's stream
+    if primary and args.dump_outputs:
+        last = slice(S - B, S)
+        dump_outputs(args.dump_outputs, {"draws": draws[last], "n_steps": n_steps[last], "tree_depth": depth[last],
+                                         "divergent": diverg[last], "accept_prob": accept[last]},
+                     rank, world, lo)
+    if not args.full:
+        out, _ = headline(model=model, d=d, K=K, W=W, B=B, adapt=args.adapt, Cper=Cper, world=world, dist=dist,
+                             dev=dev, leap_local=leap_local, div_local=div_local, elapsed_local=elapsed,
+                             epsilon=tuning["epsilon"], lanes=lanes, warm_lanes=warm_lanes,
+                             dense_mass=args.dense_mass)
+        comp.close()
+        return (out if rank == 0 else None), True
 
     # --- diagnostics: per-chain Geyer ESS on device, summed over chains; RCCL all-gather of the
     # finished traces for split R-hat (the only collective on the path) ---
@@ -679,13 +770,7 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
     comp.check(L.exmc_hip_ess(comp.h, draws.data_ptr(), S, d, Cper, ess.data_ptr()))
     ess_s = time.perf_counter() - t0      # the call returns when the kernel has finished
     ess_ms = comp.last_kernel_ms
-    # Diagnostics.ess_bulk (diagnostics.ex:60-72): rank-normalise (rank_scores_kernel) into a second
-    # trace, then the same ESS kernels on it -- BASELINE.md section 2 asks for ESS/s by both
-    essb = torch.empty((d, Cper), dtype=torch.float64, device=dev)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    comp.check(L.exmc_hip_ess_bulk(comp.h, draws.data_ptr(), S, d, Cper, essb.data_ptr()))
-    ess_bulk_s = time.perf_counter() - t0
+    essb, ess_bulk_s = bulk_ess(comp, draws, S, d, Cper)
 
     def rhat_lib(x):
         """Diagnostics.rhat (diagnostics.ex:80-115) of a [S][d][C] device trace by the library's own
@@ -709,6 +794,8 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
                            force=bool(getattr(args, "force_dist", False)) and world == 1,
                            ess_bulk=essb, ess_bulk_s=ess_bulk_s)
     if rank == 0:
+        if essb is None:
+            note_bulk_skipped(out, S)
         out["roofline"]["traffic_on_these_sources"] = counters_current(traffic_entry(model, Cper, S, lanes))
         value, local_lf = out["value"], float(leap_local)
         if model == "eight_schools":
@@ -753,7 +840,8 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
                 # (logistic, radon: a chain is ~1 s of one core; their legs stay within ~6 s each so that the
                 # whole default command stays under a minute)
                 budget = 15.0 if primary else (8.0 if model == "sv" else 3.0)
-                cb = cpu_baseline(spec, init, S, Ctot, budget_s=budget, max_chains=None if primary else 256)
+                cb = cpu_baseline(spec, init, min(S, PROTOCOL_DRAWS), Ctot, budget_s=budget,
+                                  max_chains=None if primary else 256)
                 out["cpu_baseline"] = cb
                 out["gpu_over_cpu"] = {"leapfrog_steps_per_s": value / cb["value"],
                                        "ess_per_s": out["ess_per_s"] / cb["ess_per_s"],
@@ -766,13 +854,15 @@ def run_model(args, model, rank, local_rank, world, dev, dist, barrier, primary)
 
 
 def run_model_independent(args, model, spec, comp, opts, lanes, bytes_per_leapfrog, gather_traces, rank, world,
-                          dev, dist, barrier, Cper):
+                          dev, dist, barrier, Cper, primary):
     """`--independent-warmup`: sample_chains_parallel (sampler.ex:1139-1176) as ONE launch per rank --
     chain i = sample/3 with seed 42 + 7919 i: its own step-size search, dual averaging and Welford
     windows, then its draws from the adapted position. The timed region is the whole launch; `value`
     counts every leapfrog of it (warmup and sampling), ESS/s has no separate adaptation term."""
     K, W, d = args.steps, args.warmup, spec.d
     B = args.draws_per_step
+    if not primary:
+        K = min(K, max(1, PROTOCOL_DRAWS // B))
     S = K * B
     Ctot = Cper * world
     L = comp.L
@@ -798,30 +888,20 @@ def run_model_independent(args, model, spec, comp, opts, lanes, bytes_per_leapfr
     elapsed = time.perf_counter() - t0
     kernel_ms = comp.last_kernel_ms
     warm_lf = int(tune[:, 2].sum())
-    ess = torch.empty((d, Cper), dtype=torch.float64, device=dev)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    comp.check(L.exmc_hip_ess(comp.h, draws.data_ptr(), S, d, Cper, ess.data_ptr()))
-    ess_s = time.perf_counter() - t0
-    ess_ms = comp.last_kernel_ms
-    essb = torch.empty((d, Cper), dtype=torch.float64, device=dev)
-    t0 = time.perf_counter()
-    comp.check(L.exmc_hip_ess_bulk(comp.h, draws.data_ptr(), S, d, Cper, essb.data_ptr()))
-    ess_bulk_s = time.perf_counter() - t0
-
-    def rhat_lib(x):
-        x = x.contiguous()
-        rk = torch.empty((x.shape[1],), dtype=torch.float64, device=x.device)
-        torch.cuda.synchronize()
-        comp.check(L.exmc_hip_rhat(comp.h, x.data_ptr(), x.shape[0], x.shape[1], x.shape[2], rk.data_ptr()))
-        return rk
+    if primary and args.dump_outputs:
+        last = slice(S - B, S)
+        dump_outputs(args.dump_outputs, {"draws": draws[last], "n_steps": n_steps[last], "divergent": diverg[last],
+                                         "tuning": tune.T}, rank, world, lo)
     eps = np.sort(tune[:, 0])
-    out, ok = finish_model(model=model, d=d, K=K, W=W, B=B, adapt=args.adapt, Cper=Cper, world=world, rank=rank,
-                           dist=dist, draws=draws, ess=ess, leap_local=lf.value + warm_lf, div_local=dv.value,
-                           elapsed_local=elapsed, kernel_ms=kernel_ms, adapt_s=0.0, ess_s=ess_s, ess_ms=ess_ms,
-                           epsilon=float(eps[len(eps) // 2]), lanes=lanes, warm_lanes=lanes,
-                           bytes_per_leapfrog=bytes_per_leapfrog, gather_traces=gather_traces, rhat_fn=rhat_lib,
-                           sync=torch.cuda.synchronize, ess_bulk=essb, ess_bulk_s=ess_bulk_s)
+    if not args.full:
+        out, _ = headline(model=model, d=d, K=K, W=W, B=B, adapt=args.adapt, Cper=Cper, world=world, dist=dist,
+                             dev=dev, leap_local=lf.value + warm_lf, div_local=dv.value, elapsed_local=elapsed,
+                             epsilon=float(eps[len(eps) // 2]), lanes=lanes, warm_lanes=lanes)
+        ok = True
+    else:
+        out, ok = independent_diagnostics(args, model, comp, K, B, d, Cper, world, rank, dist, dev, draws,
+                                          lf.value + warm_lf, dv.value, elapsed, kernel_ms, float(eps[len(eps) // 2]),
+                                          lanes, bytes_per_leapfrog, gather_traces)
     if rank == 0:
         out["config"]["workload"] = out["config"]["workload"].replace(
             "after one shared %d-iteration warmup" % args.adapt,
@@ -832,12 +912,43 @@ def run_model_independent(args, model, spec, comp, opts, lanes, bytes_per_leapfr
             "step_size_min_median_max": [float(eps[0]), float(eps[len(eps) // 2]), float(eps[-1])],
             "note": "value and roofline count the leapfrogs of both phases; ess_wall_s.adaptation is 0 because the "
                     "adaptation is inside the timed launch"}
-        out["reference_published"] = reference_published(model)
-        out["roofline"]["kernel"] = "indep_kernel"
+        if args.full:
+            out["reference_published"] = reference_published(model)
+            out["roofline"]["kernel"] = "indep_kernel"
         if world == 1:
             out["mean_leapfrogs_per_draw"] = lf.value / float(S * Ctot)   # the draws' own trees
     comp.close()
     return (out if rank == 0 else None), ok
+
+
+def independent_diagnostics(args, model, comp, K, B, d, Cper, world, rank, dist, dev, draws, leap_local,
+                            div_local, elapsed, kernel_ms, epsilon, lanes, bytes_per_leapfrog, gather_traces):
+    """--full of `--independent-warmup`: ESS (both kinds) and split R-hat of the finished trace, finish_model."""
+    S = K * B
+    L = comp.L
+    ess = torch.empty((d, Cper), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    comp.check(L.exmc_hip_ess(comp.h, draws.data_ptr(), S, d, Cper, ess.data_ptr()))
+    ess_s = time.perf_counter() - t0
+    ess_ms = comp.last_kernel_ms
+    essb, ess_bulk_s = bulk_ess(comp, draws, S, d, Cper)
+
+    def rhat_lib(x):
+        x = x.contiguous()
+        rk = torch.empty((x.shape[1],), dtype=torch.float64, device=x.device)
+        torch.cuda.synchronize()
+        comp.check(L.exmc_hip_rhat(comp.h, x.data_ptr(), x.shape[0], x.shape[1], x.shape[2], rk.data_ptr()))
+        return rk
+    out, ok = finish_model(model=model, d=d, K=K, W=args.warmup, B=B, adapt=args.adapt, Cper=Cper, world=world,
+                           rank=rank, dist=dist, draws=draws, ess=ess, leap_local=leap_local, div_local=div_local,
+                           elapsed_local=elapsed, kernel_ms=kernel_ms, adapt_s=0.0, ess_s=ess_s, ess_ms=ess_ms,
+                           epsilon=epsilon, lanes=lanes, warm_lanes=lanes,
+                           bytes_per_leapfrog=bytes_per_leapfrog, gather_traces=gather_traces, rhat_fn=rhat_lib,
+                           sync=torch.cuda.synchronize, ess_bulk=essb, ess_bulk_s=ess_bulk_s)
+    if out is not None and essb is None:
+        note_bulk_skipped(out, S)
+    return out, ok
 
 
 if __name__ == "__main__":

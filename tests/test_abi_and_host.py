@@ -49,14 +49,14 @@ def test_header_is_plain_c():
     assert p.returncode == 0, p.stderr
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     from exmc_amd import _lib
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "exmc_hip.h"\n'
            'int main(void){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(exmc_hip_opts),'
            'offsetof(exmc_hip_opts, seed), sizeof(exmc_hip_tuning),'
            'offsetof(exmc_hip_tuning, warmup_divergences), sizeof(exmc_hip_trace),'
            'offsetof(exmc_hip_trace, energy));return 0;}\n')
-    exe = "/tmp/exmc_layout_check"
+    exe = str(tmp_path / "exmc_layout_check")
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
                    input=src.encode(), check=True)
     got = [int(x) for x in subprocess.check_output([exe]).split()]

@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--steps", "4", "--warmup", "1", "--no-cpu", "--no-multi-step", "--no-extra-legs"]
+ARGS = ["--steps", "4", "--warmup", "1", "--full", "--no-cpu", "--no-multi-step", "--no-extra-legs"]
 
 
 def _port():

@@ -151,7 +151,7 @@ def test_bench_command_with_forced_collectives():
     line with every collective made, equal to the plain command's deterministic fields."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-            "--no-cpu", "--no-multi-step", "--no-sv-leg", "--no-extra-legs", "--chains-per-gpu", "256"]
+            "--full", "--no-cpu", "--no-multi-step", "--no-sv-leg", "--no-extra-legs", "--chains-per-gpu", "256"]
     lines = []
     for extra in ([], ["--force-dist"], ["--force-dist", "--gather-traces"]):
         r = subprocess.run(base + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)

@@ -8,7 +8,7 @@ out=gpurun_out/${1:-espipe}; mkdir -p $out
 export EXMC_HIP_LIB=${EXMC_HIP_LIB:-$PWD/exmc_amd/lib/libexmc_hip_esprobe.so}
 for cfg in "0 1" "1 0" "1 1"; do
   set -- $cfg; pipe=$1; prio=$2
-  EXMC_HIP_NUTS_PIPE=$pipe EXMC_HIP_PRIO=$prio EXMC_WAVE_PROBE_OUT=$out/waves_pipe${pipe}_prio$prio.txt python bench.py --no-cpu --no-sv-leg --no-multi-step > $out/bench_pipe${pipe}_prio$prio.json 2> $out/bench_pipe${pipe}_prio$prio.err || { tail -3 $out/bench_pipe${pipe}_prio$prio.err; exit 1; }
+  EXMC_HIP_NUTS_PIPE=$pipe EXMC_HIP_PRIO=$prio EXMC_WAVE_PROBE_OUT=$out/waves_pipe${pipe}_prio$prio.txt python bench.py --full --no-cpu --no-sv-leg --no-multi-step > $out/bench_pipe${pipe}_prio$prio.json 2> $out/bench_pipe${pipe}_prio$prio.err || { tail -3 $out/bench_pipe${pipe}_prio$prio.err; exit 1; }
   python -c "import json; d=json.load(open('$out/bench_pipe${pipe}_prio$prio.json')); print('pipe $pipe prio $prio: %.3e lf/s kernel %.2f ms eps %.6f lf %d' % (d['value'], d['roofline']['kernel_ms'], d['step_size'], d['roofline']['leapfrogs_per_launch']))"
 done
 python - <<PY

@@ -3,7 +3,7 @@
 tag=${1:-models}; shift; out=gpurun_out/$tag; mkdir -p $out
 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1; tail -2 $out/pytest.log
 for m in "$@"; do
-  python bench.py --model $m > $out/bench_$m.json 2> $out/bench_$m.err || tail -3 $out/bench_$m.err
+  python bench.py --full --model $m > $out/bench_$m.json 2> $out/bench_$m.err || tail -3 $out/bench_$m.err
   python - <<PY
 import json
 d=json.load(open("$out/bench_$m.json"))

@@ -7,9 +7,9 @@ tag=${1:-r3_end}; out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 bash tools/gpu_pmc_session.sh $tag/pmc_es --no-sv-leg > $out/pmc_es.log 2>&1 || { tail -5 $out/pmc_es.log; exit 1; }
 bash tools/gpu_pmc_session.sh $tag/pmc_sv --model sv > $out/pmc_sv.log 2>&1 || { tail -5 $out/pmc_sv.log; exit 1; }
-python bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 for m in radon logistic gen_sv gen_radon gen_logistic gen_eight_schools; do
-  python bench.py --model $m > $out/bench_$m.json 2> $out/bench_$m.err || { tail -5 $out/bench_$m.err; exit 1; }
+  python bench.py --full --model $m > $out/bench_$m.json 2> $out/bench_$m.err || { tail -5 $out/bench_$m.err; exit 1; }
 done
 python - <<PY
 import json, glob

@@ -8,7 +8,7 @@ tail -1 $out/parity.log
 for i in $(seq 1 $n); do
   for lib in "$@"; do
     v=$(basename $lib .so)
-    EXMC_HIP_LIB=$PWD/exmc_amd/lib/$lib python3 bench.py --no-sv-leg --no-cpu --no-multi-step > $out/$v.$i.json 2> $out/$v.$i.err || { tail -3 $out/$v.$i.err; exit 1; }
+    EXMC_HIP_LIB=$PWD/exmc_amd/lib/$lib python3 bench.py --full --no-sv-leg --no-cpu --no-multi-step > $out/$v.$i.json 2> $out/$v.$i.err || { tail -3 $out/$v.$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$out/$v.$i.json')); print('$v run $i: %.4e lf/s kernel %.3f ms adapt %.2f ms lf %d eps %.17g' % (d['value'], d['roofline']['kernel_ms'], 1e3*d['ess_wall_s']['adaptation'], d['roofline']['leapfrogs_per_launch'], d['step_size']))"
   done
 done

@@ -14,17 +14,17 @@ for wg in 1 0 x; do
 done
 unset EXMC_HIP_NUTS_WG
 for i in 1 2; do
-  python3 bench.py --model logistic --no-cpu --no-multi-step > $out/tree.$i.json 2> $out/tree.$i.err || { tail -5 $out/tree.$i.err; exit 1; }
+  python3 bench.py --full --model logistic --no-cpu --no-multi-step > $out/tree.$i.json 2> $out/tree.$i.err || { tail -5 $out/tree.$i.err; exit 1; }
   line $out/tree.$i.json tree
   for lib in "$@"; do
     n=$(basename $lib .so)
-    EXMC_HIP_LIB=$PWD/$lib python3 bench.py --model logistic --no-cpu --no-multi-step > $out/$n.$i.json 2> $out/$n.$i.err || { tail -5 $out/$n.$i.err; exit 1; }
+    EXMC_HIP_LIB=$PWD/$lib python3 bench.py --full --model logistic --no-cpu --no-multi-step > $out/$n.$i.json 2> $out/$n.$i.err || { tail -5 $out/$n.$i.err; exit 1; }
     line $out/$n.$i.json $n
   done
 done
-EXMC_HIP_NUTS_WG=0 python3 bench.py --model logistic --no-cpu --no-multi-step > $out/tree.onewave.json 2> $out/tree.onewave.err || { tail -5 $out/tree.onewave.err; exit 1; }
+EXMC_HIP_NUTS_WG=0 python3 bench.py --full --model logistic --no-cpu --no-multi-step > $out/tree.onewave.json 2> $out/tree.onewave.err || { tail -5 $out/tree.onewave.err; exit 1; }
 line $out/tree.onewave.json "tree, one-wave form"
 if [ $pmc = 1 ]; then
-  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY --output-format csv -d $out/pmc_tree -o run -- python3 bench.py --model logistic --no-cpu --no-multi-step > $out/pmc_tree.json 2> $out/pmc_tree.err || { tail -3 $out/pmc_tree.err; exit 1; }
+  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY --output-format csv -d $out/pmc_tree -o run -- python3 bench.py --full --model logistic --no-cpu --no-multi-step > $out/pmc_tree.json 2> $out/pmc_tree.err || { tail -3 $out/pmc_tree.err; exit 1; }
   python3 tools/pmc_kernel_table.py $out/pmc_tree nuts_kernel | tail -2
 fi

@@ -12,7 +12,7 @@ done
 for i in 1 2 3; do
   for lib in "$@"; do
     n=$(basename $lib .so)
-    EXMC_HIP_LIB=$PWD/$lib python3 bench.py --model logistic --no-cpu --no-multi-step > $out/$n.$i.json 2> $out/$n.$i.err || { tail -5 $out/$n.$i.err; exit 1; }
+    EXMC_HIP_LIB=$PWD/$lib python3 bench.py --full --model logistic --no-cpu --no-multi-step > $out/$n.$i.json 2> $out/$n.$i.err || { tail -5 $out/$n.$i.err; exit 1; }
     line $out/$n.$i.json $n
   done
 done

@@ -11,7 +11,7 @@ echo "$(basename $last .so): $(tail -1 $out/parity.log)"
 for i in 1 2 3; do
   for lib in "$@"; do
     n=$(basename $lib .so)
-    EXMC_HIP_LIB=$PWD/$lib python3 bench.py --model radon --no-cpu --no-multi-step > $out/$n.$i.json 2> $out/$n.$i.err || { tail -5 $out/$n.$i.err; exit 1; }
+    EXMC_HIP_LIB=$PWD/$lib python3 bench.py --full --model radon --no-cpu --no-multi-step > $out/$n.$i.json 2> $out/$n.$i.err || { tail -5 $out/$n.$i.err; exit 1; }
     line $out/$n.$i.json $n
   done
 done

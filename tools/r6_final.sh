@@ -9,10 +9,10 @@ tag=${1:-r6_end}; out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 timeout -k 10 900 python3 -m pytest tests -m gpu -q > $out/pytest.log 2>&1; tail -3 $out/pytest.log
 for i in 1 2; do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver_cmd_run$i.json 2> $out/driver_cmd_run$i.err || { tail -5 $out/driver_cmd_run$i.err; exit 1; }
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/driver_cmd_run$i.json 2> $out/driver_cmd_run$i.err || { tail -5 $out/driver_cmd_run$i.err; exit 1; }
 done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --force-dist > $out/force_dist.json 2> $out/force_dist.err || { tail -5 $out/force_dist.err; exit 1; }
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu > $out/bench_under_rocprof.json 2> $out/stats.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --force-dist > $out/force_dist.json 2> $out/force_dist.err || { tail -5 $out/force_dist.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu > $out/bench_under_rocprof.json 2> $out/stats.err
 cp $(find $out/stats -name '*kernel_stats.csv' | head -1) $out/kernel_stats.csv 2>/dev/null
 python3 - <<PY
 import json, glob

@@ -7,6 +7,6 @@ python3 -m pytest tests/test_gpu_codegen_lanes.py -x -q > $out/parity.log 2>&1 |
 tail -1 $out/parity.log
 for i in 1 2; do for m in gen_logistic gen_sv gen_radon; do for v in fast exact; do
   if [ $v = exact ]; then export EXMC_GEN_EXTRA_FLAGS="-DEXMC_GEN_FAST_WINDOW=0"; else unset EXMC_GEN_EXTRA_FLAGS; fi
-  python3 bench.py --model $m --no-cpu --no-multi-step > $out/$m.$v.$i.json 2> $out/$m.$v.$i.err || { tail -3 $out/$m.$v.$i.err; exit 1; }
+  python3 bench.py --full --model $m --no-cpu --no-multi-step > $out/$m.$v.$i.json 2> $out/$m.$v.$i.err || { tail -3 $out/$m.$v.$i.err; exit 1; }
   python3 -c "import json; d=json.load(open('$out/$m.$v.$i.json')); print('$m $v: kernel %.1f ms adapt %.4f s eps %.17g lf %d' % (d['roofline']['kernel_ms'], d['ess_wall_s']['adaptation'], d['step_size'], d['roofline']['leapfrogs_per_launch']))"
 done; done; done

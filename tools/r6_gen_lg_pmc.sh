@@ -4,7 +4,7 @@
 out=gpurun_out/r6_gen_lg_pmc; mkdir -p $out
 export TMPDIR=/tmp
 for m in gen_logistic logistic; do
-  run() { name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $out/$m.$name -o run -- python3 bench.py --no-cpu --no-multi-step --model $m > $out/$m.$name.json 2> $out/$m.$name.err || { tail -3 $out/$m.$name.err; exit 1; }; echo "$m $name done"; }
+  run() { name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $out/$m.$name -o run -- python3 bench.py --full --no-cpu --no-multi-step --model $m > $out/$m.$name.json 2> $out/$m.$name.err || { tail -3 $out/$m.$name.err; exit 1; }; echo "$m $name done"; }
   run insts SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_LDS
   run cycles SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY
   run lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS

@@ -9,6 +9,6 @@ tail -1 $out/parity.log
 for i in 1 2 3; do for v in fast exact; do
   m=gen_eight_schools
   if [ $v = exact ]; then export EXMC_GEN_EXTRA_FLAGS="-DEXMC_GEN_FAST_WINDOW=0"; else unset EXMC_GEN_EXTRA_FLAGS; fi
-  python3 bench.py --model $m --no-cpu --no-multi-step > $out/$m.$v.$i.json 2> $out/$m.$v.$i.err || { tail -3 $out/$m.$v.$i.err; exit 1; }
+  python3 bench.py --full --model $m --no-cpu --no-multi-step > $out/$m.$v.$i.json 2> $out/$m.$v.$i.err || { tail -3 $out/$m.$v.$i.err; exit 1; }
   python3 -c "import json; d=json.load(open('$out/$m.$v.$i.json')); print('$m $v: kernel %.2f ms adapt %.4f s eps %.17g lf %d' % (d['roofline']['kernel_ms'], d['ess_wall_s']['adaptation'], d['step_size'], d['roofline']['leapfrogs_per_launch']))"
 done; done

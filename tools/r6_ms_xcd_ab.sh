@@ -8,7 +8,7 @@ tail -1 $out/parity.log
 for i in $(seq 1 $n); do
   for v in before after; do
     lib=""; [ $v = before ] && lib=$before
-    EXMC_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --no-sv-leg --no-extra-legs --no-cpu --steps 2 --warmup 1 > $out/$v.$i.json 2> $out/$v.$i.err || { tail -3 $out/$v.$i.err; exit 1; }
+    EXMC_HIP_LIB=$lib timeout -k 10 200 python3 bench.py --full --no-sv-leg --no-extra-legs --no-cpu --steps 2 --warmup 1 > $out/$v.$i.json 2> $out/$v.$i.err || { tail -3 $out/$v.$i.err; exit 1; }
   done
 done
 python3 - <<PY

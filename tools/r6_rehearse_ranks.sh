@@ -10,11 +10,11 @@ tag=${1:-r6_rehearsal}; out=gpurun_out/$tag; mkdir -p $out
 export EXMC_BENCH_SHARED_GPU=1
 for n in 2 3; do
   timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus $n --steps 20 --warmup 5 > $out/launcher_n$n.json 2> $out/launcher_n$n.err || { echo "n=$n failed"; tail -20 $out/launcher_n$n.err; exit 1; }
+      bench.py --full --gpus $n --steps 20 --warmup 5 > $out/launcher_n$n.json 2> $out/launcher_n$n.err || { echo "n=$n failed"; tail -20 $out/launcher_n$n.err; exit 1; }
   echo "launcher n=$n: $(wc -l < $out/launcher_n$n.json) line(s) on stdout"
 done
 # without a launcher: bench.py starts its own ranks (spawn_ranks)
-timeout -k 10 400 python3 bench.py --gpus 2 --steps 20 --warmup 5 --no-extra-legs > $out/spawn_n2.json 2> $out/spawn_n2.err || { echo "spawn failed"; tail -20 $out/spawn_n2.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-extra-legs > $out/spawn_n2.json 2> $out/spawn_n2.err || { echo "spawn failed"; tail -20 $out/spawn_n2.err; exit 1; }
 echo "spawn n=2: $(wc -l < $out/spawn_n2.json) line(s) on stdout"
 python3 - <<PY
 import json, glob

@@ -2,7 +2,7 @@
 # sv at the protocol with chain migration off / on (same box): gpurun_out/$1/
 out=gpurun_out/${1:-sv_mig}; mkdir -p $out
 for mig in 0 1 1; do
-  EXMC_HIP_MIGRATE_STATS=1 EXMC_HIP_MIGRATE=$mig timeout -k 10 300 python bench.py --model sv --no-multi-step --no-cpu > $out/bench_mig$mig.json 2> $out/bench_mig$mig.err || exit 1
+  EXMC_HIP_MIGRATE_STATS=1 EXMC_HIP_MIGRATE=$mig timeout -k 10 300 python bench.py --full --model sv --no-multi-step --no-cpu > $out/bench_mig$mig.json 2> $out/bench_mig$mig.err || exit 1
   grep migrate $out/bench_mig$mig.err | tail -1
   python - <<PY
 import json
