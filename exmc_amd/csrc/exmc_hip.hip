@@ -202,6 +202,7 @@ struct exmc_hip_model {
   DevBuf flat;      // perm[D], rank[D] (int32) when the kernel order is not the reference's flat order
   bool flat_set = false;
   DevBuf tuning;    // inv_mass[D], sqrt_inv_mass[D]
+  DevBuf ms_mass;   // exmc_hip_multi_step's inv_mass[D]: the caller's, never the resident chains'
   DevBuf state;     // q[D][C], g[D][C], logp[C], rng[2][C]
   DevBuf stack;
   DevBuf misc;      // [0] eps_out, [1..2] counters (u64), [3] trace scratch word, [8..8+D) init_q
@@ -224,13 +225,17 @@ struct exmc_hip_model {
   DevBuf esswork;   // ESS: [count | EssTailItem...] of the series that go on to ess_tail_kernel
   bool dense_on = false;
   int state_chains = 0;
-  // resident chains (exmc_hip_chains_init / _advance)
+  // resident chains (exmc_hip_chains_init / _advance, exmc_hip_stream_begin / _next / _start) and
+  // the call that created them: only that owner's continuation calls advance them
   int res_C = 0, res_lanes = 0, res_max_depth = 10;
+  int res_owner = 0;   // kResNone / kResChains / kResStream
   double res_eps = 0.0;
   int simds = 1024;   // 4 x the device's compute units (MI355X: 256 CUs)
 };
 
 namespace {
+
+enum { kResNone = 0, kResChains = 1, kResStream = 2 };
 
 ChainState state_view(exmc_hip_model* m, int C) {
   ChainState s;
@@ -546,10 +551,11 @@ template <> inline constexpr bool kStreamKernel<Custom<EXMC_GEN_LANES>> = true;
 #endif
 #endif
 
-int launch_nuts(exmc_hip_model* m, int lanes, int C, int n_draws, int draw_offset, double eps,
+// dense: run under the dense mass installed on the handle (m->dense) instead of m->tuning's diagonal
+int launch_nuts(exmc_hip_model* m, bool dense, int lanes, int C, int n_draws, int draw_offset, double eps,
                 int max_depth, TraceDev tr, bool timed, int* progress = nullptr) {
   if (max_depth < 1 || max_depth > kMaxLevels) return fail(EXMC_ERR_BADARG, "max_tree_depth out of range");
-  return dispatch_mass(m, lanes, m->dense_on, [&](auto tag, const auto& mc) {
+  return dispatch_mass(m, lanes, dense, [&](auto tag, const auto& mc) {
     using T = decltype(tag);
     using M = typename T::M;
     dim3 grid = grid_for(C, T::G, kNutsBlock);
@@ -607,7 +613,7 @@ int launch_nuts(exmc_hip_model* m, int lanes, int C, int n_draws, int draw_offse
         P.mig = m->migboard.as<int>();
       }
     }
-    if (m->dense_on) {
+    if (dense) {
       if (T::G != 1 && !M::kRowDense && !M::kLaneDense)
         return fail(EXMC_ERR_UNSUPPORTED, "no dense mass matrix for this model at this lanes_per_chain");
       P.dm.cov = m->dense.as<double>();
@@ -650,7 +656,7 @@ int launch_nuts(exmc_hip_model* m, int lanes, int C, int n_draws, int draw_offse
       const char* we = std::getenv("EXMC_HIP_NUTS_WG");
       const size_t waves = grid.x;
       const bool on = we ? (we[0] == '1') : ((int)waves > (m->simds > 0 ? m->simds : 1024));
-      if (on && !m->dense_on && M::wg_ok(mc)) {
+      if (on && !dense && M::wg_ok(mc)) {
         const dim3 wgrid((unsigned)((waves + W - 1) / W));
         const size_t wthreads = (size_t)wgrid.x * W * kNutsBlock;
         constexpr int kSpillW = (kMaxLevels > WL) ? (kMaxLevels - WL) : 1;
@@ -868,7 +874,7 @@ int warmup_transition(exmc_hip_model* m, int lanes, double eps, int max_depth, s
   tr.draws = m->trace.as<double>();
   tr.accept_prob = m->trace.as<double>() + d;
   tr.divergent = (int32_t*)(m->trace.as<double>() + d + 1);
-  rc = launch_nuts(m, lanes, 1, 1, 0, eps, max_depth, tr, false);
+  rc = launch_nuts(m, false, lanes, 1, 1, 0, eps, max_depth, tr, false);
   if (rc) return rc;
   std::vector<double> h(d + 2);
   HIP_TRY(hipMemcpyAsync(h.data(), m->trace.p, (size_t)(d + 2) * 8, hipMemcpyDeviceToHost, m->stream));
@@ -1435,7 +1441,7 @@ void exmc_hip_model_destroy(exmc_hip_model* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);   // a stream run may still be writing its page-locked trace
-  m->zig.release(); m->tuning.release(); m->state.release(); m->stack.release();
+  m->zig.release(); m->tuning.release(); m->ms_mass.release(); m->state.release(); m->stack.release();
   m->misc.release(); m->trace.release(); m->io.release(); m->data.release(); m->flat.release(); m->scores.release(); m->dense.release(); m->esswork.release();
   m->densep.release(); m->densews.release(); m->migboard.release();
   if (m->ev0) (void)hipEventDestroy(m->ev0);
@@ -1518,12 +1524,15 @@ int exmc_hip_multi_step(exmc_hip_model* m, const double* q, const double* p, con
     return fail(EXMC_ERR_BADARG, "bad arguments");
   HIP_TRY(hipSetDevice(m->device));
   lanes = resolve_lanes(m, lanes);
-  int rc = upload_tuning(m, inv_mass_host);
+  // a buffer of its own: m->tuning is the inverse mass resident chains continue under
+  int rc = m->ms_mass.ensure((size_t)m->d * 8);
   if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(m->ms_mass.p, inv_mass_host, (size_t)m->d * 8, hipMemcpyHostToDevice, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
   MultiStepParams P;
   P.q = q; P.p = p; P.g = g;
   P.eps = eps;
-  P.inv_mass = m->tuning.as<double>();
+  P.inv_mass = m->ms_mass.as<double>();
   P.n_steps = n_steps;
   P.n_chains = n_chains;
   P.all_q = all_q; P.all_p = all_p; P.all_g = all_g; P.all_logp = all_logp;
@@ -1611,7 +1620,9 @@ int exmc_hip_transitions_host(exmc_hip_model* m, double* q, double* logp, double
   if (rc) return rc;
   rc = reset_counters(m);
   if (rc) return rc;
-  rc = launch_nuts(m, lanes, C, n_draws, 0, eps, max_depth, trace_view(m->trace.p, L), true);
+  // the explicit inv_mass is the whole mass of this call: a dense mass installed on the handle is
+  // not read (and stays installed)
+  rc = launch_nuts(m, false, lanes, C, n_draws, 0, eps, max_depth, trace_view(m->trace.p, L), true);
   if (rc) return rc;
   rc = finish_timing(m);
   if (rc) return rc;
@@ -1641,6 +1652,9 @@ int warmup_impl(exmc_hip_model* m, const double* init_q, exmc_hip_opts o, const 
       if (!(start->inv_mass[i] > 0.0)) return fail(EXMC_ERR_BADARG, "warm start needs a positive inverse mass");
   }
   HIP_TRY(hipSetDevice(m->device));
+  // a warmup adapts a diagonal mass from its own start: a dense mass installed by an earlier call
+  // belongs to that call's tuning (and would otherwise reach the sampling that follows this one)
+  m->dense_on = false;
   // lanes_per_chain = 0: the library's layout for the one-chain warmup (logistic, generated lane
   // layouts of fewer than 64 lanes: the whole wavefront), not the sampling default
   int lanes = o.lanes_per_chain > 0 ? o.lanes_per_chain : exmc_hip_model_default_warmup_lanes(m);
@@ -1700,6 +1714,7 @@ int exmc_hip_model_set_dense_mass(exmc_hip_model* m, const double* cov, const do
 
 int exmc_hip_model_clear_dense_mass(exmc_hip_model* m) {
   if (check_model(m)) return EXMC_ERR_BADARG;
+  if (m->dense_on) m->res_C = 0;   // the resident chains ran under the dense mass
   m->dense_on = false;
   return EXMC_OK;
 }
@@ -1739,6 +1754,7 @@ int exmc_hip_chains_init(exmc_hip_model* m, const exmc_hip_tuning* tuning, const
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(m->stream));
   m->res_C = C;
+  m->res_owner = kResChains;
   m->res_lanes = lanes;
   m->res_eps = tuning->epsilon;
   m->res_max_depth = o.max_tree_depth;
@@ -1748,7 +1764,8 @@ int exmc_hip_chains_init(exmc_hip_model* m, const exmc_hip_tuning* tuning, const
 int exmc_hip_chains_advance(exmc_hip_model* m, int n_draws, int row_offset, exmc_hip_trace tr,
                             int64_t* leapfrogs, int32_t* divergences) {
   if (check_model(m)) return EXMC_ERR_BADARG;
-  if (m->res_C < 1) return fail(EXMC_ERR_BADARG, "no resident chains: call exmc_hip_chains_init");
+  if (m->res_C < 1 || m->res_owner != kResChains)
+    return fail(EXMC_ERR_BADARG, "no resident chains: call exmc_hip_chains_init");
   if (n_draws < 0 || row_offset < 0) return fail(EXMC_ERR_BADARG, "bad arguments");
   HIP_TRY(hipSetDevice(m->device));
   int rc = reset_counters(m);
@@ -1756,7 +1773,7 @@ int exmc_hip_chains_advance(exmc_hip_model* m, int n_draws, int row_offset, exmc
   TraceDev t;
   t.draws = tr.draws; t.logp = tr.logp; t.tree_depth = tr.tree_depth; t.n_steps = tr.n_steps;
   t.divergent = tr.divergent; t.accept_prob = tr.accept_prob; t.energy = tr.energy;
-  rc = launch_nuts(m, m->res_lanes, m->res_C, n_draws, row_offset, m->res_eps, m->res_max_depth, t,
+  rc = launch_nuts(m, m->dense_on, m->res_lanes, m->res_C, n_draws, row_offset, m->res_eps, m->res_max_depth, t,
                    true);
   if (rc) return rc;
   rc = finish_timing(m);
@@ -1829,7 +1846,7 @@ int exmc_hip_sample_warm_host(exmc_hip_model* m, const double* init_q, exmc_hip_
   if (rc) return rc;
   rc = reset_counters(m);
   if (rc) return rc;
-  rc = launch_nuts(m, lanes, 1, o.num_samples, 0, tun.epsilon, o.max_tree_depth,
+  rc = launch_nuts(m, false, lanes, 1, o.num_samples, 0, tun.epsilon, o.max_tree_depth,
                    trace_view(m->trace.p, L), true);
   if (rc) return rc;
   rc = finish_timing(m);
@@ -1914,7 +1931,7 @@ int exmc_hip_sample_dense_host(exmc_hip_model* m, const double* init_q, exmc_hip
   if (rc) return rc;
   rc = reset_counters(m);
   if (rc) return rc;
-  rc = launch_nuts(m, lanes, 1, o.num_samples, 0, tun.epsilon, o.max_tree_depth, trace_view(m->trace.p, L), true);
+  rc = launch_nuts(m, true, lanes, 1, o.num_samples, 0, tun.epsilon, o.max_tree_depth, trace_view(m->trace.p, L), true);
   if (rc) return rc;
   rc = finish_timing(m);
   if (rc) return rc;
@@ -1939,6 +1956,7 @@ int exmc_hip_stream_begin(exmc_hip_model* m, const double* init_q, exmc_hip_opts
   // the warmup chain stays resident and is advanced on demand (same state the one-launch
   // exmc_hip_sample_host continues from)
   m->res_C = 1;
+  m->res_owner = kResStream;
   m->res_lanes = resolve_lanes(m, o.lanes_per_chain);
   m->res_eps = tun.epsilon;
   m->res_max_depth = o.max_tree_depth;
@@ -1949,7 +1967,7 @@ int exmc_hip_stream_begin(exmc_hip_model* m, const double* init_q, exmc_hip_opts
 int exmc_hip_stream_next_host(exmc_hip_model* m, int n_draws, exmc_hip_trace tr,
                               int32_t* divergences) {
   if (check_model(m)) return EXMC_ERR_BADARG;
-  if (m->res_C != 1) return fail(EXMC_ERR_BADARG, "no stream: call exmc_hip_stream_begin");
+  if (m->res_C != 1 || m->res_owner != kResStream) return fail(EXMC_ERR_BADARG, "no stream: call exmc_hip_stream_begin");
   if (n_draws < 1) return fail(EXMC_ERR_BADARG, "n_draws must be >= 1");
   HIP_TRY(hipSetDevice(m->device));
   TraceLayout L = trace_layout(n_draws, m->d, 1);
@@ -1957,7 +1975,7 @@ int exmc_hip_stream_next_host(exmc_hip_model* m, int n_draws, exmc_hip_trace tr,
   if (rc) return rc;
   rc = reset_counters(m);
   if (rc) return rc;
-  rc = launch_nuts(m, m->res_lanes, 1, n_draws, 0, m->res_eps, m->res_max_depth,
+  rc = launch_nuts(m, false, m->res_lanes, 1, n_draws, 0, m->res_eps, m->res_max_depth,
                    trace_view(m->trace.p, L), true);
   if (rc) return rc;
   rc = finish_timing(m);
@@ -1973,7 +1991,7 @@ namespace {
 // the body of exmc_hip_stream_start once the handle is claimed
 int stream_start_claimed(exmc_hip_model* m, int n_draws, exmc_hip_trace* view,
                          const volatile int32_t** progress) {
-  if (m->res_C != 1) return fail(EXMC_ERR_BADARG, "no stream: call exmc_hip_stream_begin");
+  if (m->res_C != 1 || m->res_owner != kResStream) return fail(EXMC_ERR_BADARG, "no stream: call exmc_hip_stream_begin");
   if (n_draws < 1 || !view || !progress) return fail(EXMC_ERR_BADARG, "bad arguments");
   if (m->dense_on) return fail(EXMC_ERR_UNSUPPORTED, "a push-style stream runs under the diagonal mass");
   HIP_TRY(hipSetDevice(m->device));
@@ -1991,7 +2009,7 @@ int stream_start_claimed(exmc_hip_model* m, int n_draws, exmc_hip_trace* view,
   HIP_TRY(hipHostGetDevicePointer(&dev, m->pin_host, 0));
   int rc = reset_counters(m);
   if (rc) return rc;
-  rc = launch_nuts(m, m->res_lanes, 1, n_draws, 0, m->res_eps, m->res_max_depth,
+  rc = launch_nuts(m, false, m->res_lanes, 1, n_draws, 0, m->res_eps, m->res_max_depth,
                    trace_view((char*)dev + 64, L), true, (int*)dev);
   if (rc) return rc;
   // with one chain the device layout [draw][dim][chain] is the host layout [draw][dim]

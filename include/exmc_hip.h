@@ -104,6 +104,26 @@ int exmc_hip_device_count(void);
  * lane 16 observation slots). Free variables are in "kernel order" (DESIGN.md section 2). */
 int exmc_hip_model_create(int kind, int d, const double* data, int n_data, int device,
                           exmc_hip_model** out);
+/* Handle state. A handle serves one caller at a time: calls on one handle must not overlap.
+ * Between calls a handle carries exactly two settings:
+ *   - the flat order (exmc_hip_model_set_flat_order), read by every call that draws from the RNG;
+ *   - an installed dense mass (cov, chol), set by exmc_hip_model_set_dense_mass,
+ *     exmc_hip_warmup_dense and exmc_hip_sample_dense_host. Only exmc_hip_sample_chains[_host] and
+ *     exmc_hip_chains_init / _advance read it. exmc_hip_transitions_host does not: it runs under
+ *     exactly the inv_mass it is given, and the dense mass stays installed.
+ * Every call that adapts its own mass starts diagonal and removes an installed dense mass:
+ * exmc_hip_warmup, _warmup_from, _sample_host, _sample_warm_host, _stream_begin and
+ * _sample_independent[_host]; so does exmc_hip_model_clear_dense_mass. Every other output of a
+ * call depends on its own arguments and these two settings only.
+ * Resident chains belong to the call that created them: exmc_hip_chains_init (and
+ * exmc_hip_sample_chains[_host], which call it) or exmc_hip_stream_begin. Only the owner's
+ * continuation advances them -- exmc_hip_chains_advance for the former, exmc_hip_stream_next_host /
+ * _stream_start for the latter; the other continuation returns EXMC_ERR_BADARG. Every call that
+ * lays out chains of its own (warmups, transitions_host, sample_host / _warm / _dense,
+ * sample_independent) or changes what resident chains run under evicts them: set_flat_order,
+ * set_dense_mass, and clear_dense_mass when a dense mass was installed. exmc_hip_logp_grad_host,
+ * exmc_hip_multi_step[_host] (its inv_mass is its own), the diagnostics (ess, ess_bulk, rhat) and
+ * the accessors leave them in place. After an eviction both continuations return EXMC_ERR_BADARG. */
 void exmc_hip_model_destroy(exmc_hip_model* m);
 /* Replaces PointMap.build's layout decision (lib/exmc/point_map.ex:30-60: free RVs sorted by id
  * as strings) for the RNG-consuming steps: init_position (sampler.ex:339-349) and
@@ -140,14 +160,16 @@ int exmc_hip_logp_grad_host(exmc_hip_model* m, const double* q, int n_chains, in
 int exmc_hip_multi_step(exmc_hip_model* m, const double* q, const double* p, const double* g,
                         double eps, const double* inv_mass_host, int n_steps, int n_chains,
                         int lanes, double* all_q, double* all_p, double* all_logp, double* all_g);
-/* Host form, reference layout: q,p,g [C][d]; outputs [C][n][d], [C][n]. */
+/* Host form, reference layout: q,p,g [C][d]; outputs [C][n][d], [C][n]. Neither form changes
+ * the inverse mass that resident chains run under. */
 int exmc_hip_multi_step_host(exmc_hip_model* m, const double* q, const double* p, const double* g,
                              double eps, const double* inv_mass, int n_steps, int n_chains,
                              int lanes, double* all_q, double* all_p, double* all_logp,
                              double* all_g);
 
 /* One NUTS transition per chain from explicit state, for parity tests of Tree.build/12
- * (lib/exmc/nuts/tree.ex:65-151) + nuts_step_with_stats (sampler.ex:854-925).
+ * (lib/exmc/nuts/tree.ex:65-151) + nuts_step_with_stats (sampler.ex:854-925). Runs under the
+ * diagonal inv_mass given, whatever dense mass the handle carries; evicts resident chains.
  * Host in/out: q [C][d], logp [C], grad [C][d], rng [C][2] (exsss words a,b). */
 int exmc_hip_transitions_host(exmc_hip_model* m, double* q, double* logp, double* grad,
                               uint64_t* rng, int n_chains, int n_draws, double eps,
@@ -164,9 +186,10 @@ int exmc_hip_warmup(exmc_hip_model* m, const double* init_q, exmc_hip_opts opts,
  * leapfrog.ex:39-61). Warmup with dense Welford windows of base max(25, 10 d): tuning gets epsilon and
  * inv_mass = diag(cov) (stats.inv_mass_diag, sampler.ex:236-240), cov / chol (caller-owned, row-major
  * d x d) the covariance M^-1 and its lower Cholesky factor (the tuning map's :chol_cov). The dense
- * mass then stays in force on the handle -- momentum p = L^-T z, M^-1 p by the dense product, the
- * U-turn rule through v = M^-1 rho -- for sample_chains / chains_advance / sample_host / stream until
- * exmc_hip_model_clear_dense_mass. exmc_hip_model_set_dense_mass installs a (cov, chol) pair from an
+ * mass then stays installed on the handle -- momentum p = L^-T z, M^-1 p by the dense product, the
+ * U-turn rule through v = M^-1 rho -- for sample_chains / chains_init / chains_advance until
+ * exmc_hip_model_clear_dense_mass or a call that adapts its own (diagonal) mass removes it (sample_host
+ * and the stream are such calls; see "Handle state" above). exmc_hip_model_set_dense_mass installs a (cov, chol) pair from an
  * earlier run (sample_compiled_tuned with tuning.chol_cov). cov and chol are indexed by the entries
  * of the reference's FLAT vector (the order exmc_hip_model_set_flat_order states; sampler.ex:682-705
  * feeds Welford the flat q), tuning->inv_mass stays in kernel order. Layouts: lanes_per_chain = 1

@@ -309,3 +309,36 @@ def test_generated_model_through_the_nif(hip, mods):
         # a kind the plug-in does not carry is its own error, through its own last_error
         bad = hn.call("model_create_plugin", spec.lib_path, np.zeros(spec.data.size + 3))
         assert bad[0] == H.Atom("error") and "data length" in bad[1]
+
+
+def test_dense_sample_leaves_nothing_for_warmup_and_sample_chains(hip, mods):
+    """HipSampler.sample_chains_vectorized/3 (hip_sampler.ex:125-134: HipNative.warmup, then
+    HipNative.sample_chains) on a ref that ran sample_dense before = on a fresh ref, bit for bit: the
+    diagonal warmup removes the dense mass the earlier run installed (include/exmc_hip.h, "Handle
+    state")."""
+    hn = mods["HipNative"]
+    spec = models.eight_schools()
+    q0 = spec.to_unconstrained(spec.default_init)
+
+    def new_ref():
+        ok, ref = hn.call("model_create", spec.kind, spec.data)
+        assert ok == H.Atom("ok")
+        assert hn.call("model_set_flat_order", ref, spec.flat_order()) == H.Atom("ok")
+        return ref
+
+    used, fresh = new_ref(), new_ref()
+    trd, tund, _ = hn.call("sample_dense", used, q0, 300, 10, 10, 0.8, 13, 0)
+    cov = H.f64(tund["cov"]).reshape(spec.d, spec.d)
+    assert np.abs(cov - np.diag(np.diag(cov))).max() > 0          # a dense mass that would show
+    runs = []
+    for ref in (used, fresh):
+        tun = hn.call("warmup", ref, q0, 150, 10, 0.8, 42)
+        tr, lf, dv = hn.call("sample_chains", ref, tun["epsilon"], H.f64(tun["inv_mass"]), q0, 6, 0, 6, 30, 10, 42)
+        runs.append((tun, tr, lf, dv))
+    (tu, tru, lfu, dvu), (tf, trf, lff, dvf) = runs
+    assert tu["epsilon"] == tf["epsilon"] and np.array_equal(H.f64(tu["inv_mass"]), H.f64(tf["inv_mass"]))
+    for k in ("draws", "logp", "accept_prob", "energy"):
+        assert np.array_equal(H.f64(tru[k]), H.f64(trf[k])), k
+    for k in ("tree_depth", "n_steps", "divergent"):
+        assert np.array_equal(H.i32(tru[k]), H.i32(trf[k])), k
+    assert (lfu, dvu) == (lff, dvf)
