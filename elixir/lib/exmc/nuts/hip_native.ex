@@ -29,7 +29,7 @@ defmodule Exmc.NUTS.HipNative do
     end
   end
 
-  @doc "kind: 1 simple, 2 eight_schools, 3 sv, 4 logistic, 5 radon (include/exmc_hip.h); data: f64 binary. -> {:ok, ref} | {:error, message}"
+  @doc "kind: 1 simple, 2 eight_schools, 3 sv, 4 logistic, 5 radon, 7 sv non-centred (sv as compile_for_sampling(ir, ncp: true) rewrites it; data r[100] like 3) (include/exmc_hip.h); data: f64 binary. -> {:ok, ref} | {:error, message}"
   def model_create(_kind, _data), do: :erlang.nif_error(:nif_not_loaded)
 
   @doc "A model generated from its Builder IR: path of the plug-in library, the generator's data vector. -> {:ok, ref} | {:error, message}"

@@ -55,7 +55,7 @@ import time
 import numpy as np
 
 from . import build as _build
-from .models import ModelSpec
+from .models import ModelSpec, invert_ncp_init, reconstruct_ncp
 
 CUSTOM = 6
 MAX_D = 20   # one lane per chain: 5*D+3 doubles per tree node, one level must fit LDS
@@ -1617,7 +1617,7 @@ class GeneratedSpec(ModelSpec):
     loads instead of libexmc_hip.so."""
 
     def __init__(self, gen, lib_path, name="generated", default_init=None):
-        super().__init__(CUSTOM, name, gen.data, gen.var_names, gen.transforms, default_init)
+        super().__init__(CUSTOM, name, gen.data, gen.var_names, gen.transforms, default_init, gen.ncp_info)
         self.gen = gen
         self.lib_path = lib_path
         self.vector_entries = dict(getattr(gen, "vector_entries", {}))   # id -> (offset, length)
@@ -1644,12 +1644,7 @@ class GeneratedSpec(ModelSpec):
                 vals.update({"%s[%d]" % (k, i): float(x) for i, x in enumerate(a)})
             else:
                 vals[k] = float(v)
-        raw = {}
-        for id_, src in self.gen.ncp_info.items():
-            if id_ in vals:
-                res = lambda s: vals[s] if isinstance(s, str) else float(s)   # noqa: E731
-                raw[id_] = (vals[id_] - res(src["mu"])) / res(src["sigma"])
-        vals.update(raw)
+        vals = invert_ncp_init(vals, self.gen.ncp_info)
         q = np.zeros(self.d)
         for i, name in enumerate(self.var_names):
             x = vals[name]
@@ -1676,19 +1671,10 @@ class GeneratedSpec(ModelSpec):
                 x[..., i] = sp(x[..., i])
             elif t == "logit":
                 x[..., i] = np.exp(-sp(-x[..., i]))
-        idx = {n: i for i, n in enumerate(self.var_names)}
-        done, pending = set(), dict(self.gen.ncp_info)
-        while pending:
-            ready = [i for i, s in pending.items()
-                     if all(not (isinstance(v, str) and v in pending) for v in s.values())]
-            if not ready:
-                raise CodegenError("cyclic non-centred references")
-            for id_ in ready:
-                s = pending.pop(id_)
-                val = lambda v: x[..., idx[v]] if isinstance(v, str) else float(v)   # noqa: E731
-                x[..., idx[id_]] = val(s["mu"]) + val(s["sigma"]) * x[..., idx[id_]]
-                done.add(id_)
-        return x
+        try:
+            return reconstruct_ncp(x, self.var_names, self.gen.ncp_info)
+        except ValueError as e:
+            raise CodegenError(str(e))
 
 
 def compile_ir(ir, ncp=True, name="generated", default_init=None, verbose=False, rewrite_passes=False,

@@ -171,6 +171,91 @@ __device__ __forceinline__ double sum_xor32(double v) {
                               __builtin_amdgcn_ds_bpermute(a, __double2loint(v)));
 #endif
 }
+// lane l <- lane l ^ 16 / l ^ 32: one swap of each dword. permlane16_swap(x, x) returns the first
+// operand after the swap (its odd rows now hold the even rows of the second) and the second (its
+// even rows hold the odd rows of the first): the partner's value is the first in odd rows and the
+// second in even rows; permlane32_swap likewise with the upper and the lower half.
+__device__ __forceinline__ double swap_xor16(double v) {
+#if EXMC_XROW_PERMLANE
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  return (threadIdx.x & 16) ? __hiloint2double((int)rh[0], (int)rl[0]) : __hiloint2double((int)rh[1], (int)rl[1]);
+#else
+  const int a = (((int)threadIdx.x & 63) ^ 16) << 2;
+  return __hiloint2double(__builtin_amdgcn_ds_bpermute(a, __double2hiint(v)),
+                          __builtin_amdgcn_ds_bpermute(a, __double2loint(v)));
+#endif
+}
+__device__ __forceinline__ double swap_xor32(double v) {
+#if EXMC_XROW_PERMLANE
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return (threadIdx.x & 32) ? __hiloint2double((int)rh[0], (int)rl[0]) : __hiloint2double((int)rh[1], (int)rl[1]);
+#else
+  const int a = (((int)threadIdx.x & 63) ^ 32) << 2;
+  return __hiloint2double(__builtin_amdgcn_ds_bpermute(a, __double2hiint(v)),
+                          __builtin_amdgcn_ds_bpermute(a, __double2loint(v)));
+#endif
+}
+
+// ---- prefix and suffix sums over a 64-lane chain group, N register slots (dimension k 64 + l in
+// slot k of lane l). The association order is part of the numeric contract (the sv_ncp checker
+// restates it); every stage is a select, never a multiplication by 0, so a value past the data
+// (the caller's zeros) cannot meet an infinity in a product.
+// wave_scan_fwd: lane l of slot k ends with v_0 + ... + v_{64k+l}:
+//   1. inside each 16-lane row, Hillis-Steele: for d = 1, 2, 4, 8 a lane whose row position is >= d
+//      adds the value d lanes below (row_shr:d);
+//   2. the row totals (row position 15, row_newbcast:15): rows 1 and 3 add the total of the row below
+//      (v_permlane16_swap), then rows 2 and 3 add (total 0 + total 1) (v_permlane32_swap);
+//   3. slot k adds the last lane of slot k - 1 (after its own carry).
+// wave_scan_bwd: the mirror image, lane l of slot k ends with v_{64k+l} + ... + v_{64N-1}: row_shl:d,
+// totals at row position 0, rows 0 and 2 add the row above, rows 0 and 1 add (total 2 + total 3),
+// slot k adds lane 0 of slot k + 1.
+template <int N>
+__device__ __forceinline__ void wave_scan_fwd(double (&v)[N]) {
+  const int lane = threadIdx.x & 63, lr = lane & 15;
+#define EXMC_SCAN_STAGE(DD)                                                       \
+  _Pragma("unroll") for (int k = 0; k < N; k++) {                               \
+    const double m = dpp_move<0x110 + DD>(v[k]); /* row_shr:DD */                 \
+    v[k] = (lr >= DD) ? v[k] + m : v[k];                                          \
+  }
+  EXMC_SCAN_STAGE(1) EXMC_SCAN_STAGE(2) EXMC_SCAN_STAGE(4) EXMC_SCAN_STAGE(8)
+#undef EXMC_SCAN_STAGE
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const double t = dpp_move<0x15F>(v[k]);   // row_newbcast:15
+    const double p = swap_xor16(t);
+    v[k] = (lane & 16) ? v[k] + p : v[k];
+    const double p2 = swap_xor32(t + p);
+    v[k] = (lane & 32) ? v[k] + p2 : v[k];
+  }
+#pragma unroll
+  for (int k = 1; k < N; k++) v[k] = v[k] + readlane_f64(v[k - 1], 63);
+}
+template <int N>
+__device__ __forceinline__ void wave_scan_bwd(double (&v)[N]) {
+  const int lane = threadIdx.x & 63, lr = lane & 15;
+#define EXMC_SCAN_STAGE(DD)                                                       \
+  _Pragma("unroll") for (int k = 0; k < N; k++) {                               \
+    const double m = dpp_move<0x100 + DD>(v[k]); /* row_shl:DD */                 \
+    v[k] = (lr + DD < 16) ? v[k] + m : v[k];                                      \
+  }
+  EXMC_SCAN_STAGE(1) EXMC_SCAN_STAGE(2) EXMC_SCAN_STAGE(4) EXMC_SCAN_STAGE(8)
+#undef EXMC_SCAN_STAGE
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const double t = dpp_move<0x150>(v[k]);   // row_newbcast:0
+    const double p = swap_xor16(t);
+    v[k] = (lane & 16) ? v[k] : v[k] + p;
+    const double p2 = swap_xor32(t + p);
+    v[k] = (lane & 32) ? v[k] : v[k] + p2;
+  }
+#pragma unroll
+  for (int k = N - 2; k >= 0; k--) v[k] = v[k] + readlane_f64(v[k + 1], 0);
+}
+
 // lane l <- lane l ^ 4: two masked DPP moves per dword (row_shr:4 into the banks whose lanes have
 // bit 2 set, row_shl:4 into the others) instead of a ds_swizzle
 __device__ __forceinline__ int xor4_b32(int x) {

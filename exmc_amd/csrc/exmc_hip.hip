@@ -350,6 +350,9 @@ int dispatch(exmc_hip_model* m, int lanes, F&& f) {
         default: break;
       }
       break;
+    case EXMC_MODEL_SV_NCP:
+      if (lanes == 64) return f(Tag<SVNcp<64>, 64, 3>{}, m->sv);
+      break;
     case EXMC_MODEL_LOGISTIC:
       switch (lanes) {
         case 4: return f(Tag<Logistic<4>, 4, 2>{}, m->lg);   // matrix-core path
@@ -378,6 +381,7 @@ int dispatch(exmc_hip_model* m, int lanes, F&& f) {
 bool dense_layout_ok(const exmc_hip_model* m, int lanes) {
   return lanes == 1 || (m->kind == EXMC_MODEL_EIGHT_SCHOOLS && lanes == 16) ||
          (m->kind == EXMC_MODEL_SV && lanes == 64) || (m->kind == EXMC_MODEL_RADON && lanes == 64) ||
+         (m->kind == EXMC_MODEL_SV_NCP && lanes == 64) ||
          (m->kind == EXMC_MODEL_LOGISTIC && lanes == 16);
 }
 
@@ -411,6 +415,8 @@ int dispatch_mass(exmc_hip_model* m, int lanes, bool dense, F&& f) {
     return f(Tag<RowDenseModel<EightSchools<16>>, 16, 6>{}, m->es);
   if (dense && m->kind == EXMC_MODEL_SV && lanes == 64)
     return f(Tag<LaneDenseModel<SV<64>, 64>, 64, 2>{}, m->sv);
+  if (dense && m->kind == EXMC_MODEL_SV_NCP && lanes == 64)
+    return f(Tag<LaneDenseModel<SVNcp<64>, 64>, 64, 2>{}, m->sv);
   if (dense && m->kind == EXMC_MODEL_RADON && lanes == 64)
     return f(Tag<LaneDenseModel<Radon<64>, 64>, 64, 2>{}, m->rd);
   if (dense && m->kind == EXMC_MODEL_LOGISTIC && lanes == 16)
@@ -424,6 +430,7 @@ int default_lanes(int kind) {
     case EXMC_MODEL_EIGHT_SCHOOLS: return 16;
     case EXMC_MODEL_SIMPLE: return 1;
     case EXMC_MODEL_SV: return 64;
+    case EXMC_MODEL_SV_NCP: return 64;
     case EXMC_MODEL_LOGISTIC: return 16;
     case EXMC_MODEL_RADON: return 64;
 #if defined(EXMC_GEN_LANES)
@@ -481,7 +488,7 @@ int set_flat_order(exmc_hip_model* m, const int32_t* perm) {
 // the kinds whose free-RV names the kind fixes: ids sorted as strings (point_map.ex:37)
 int default_flat_order(exmc_hip_model* m) {
   std::vector<std::string> names;
-  if (m->kind == EXMC_MODEL_SV) {          // kernel order s_1..s_T, sigma, nu
+  if (m->kind == EXMC_MODEL_SV || m->kind == EXMC_MODEL_SV_NCP) {   // kernel order s_1..s_T (z_t), sigma, nu
     for (int t = 1; t <= m->d - 2; t++) names.push_back("s_" + std::to_string(t));
     names.push_back("sigma");
     names.push_back("nu");
@@ -536,6 +543,7 @@ template <class M> inline constexpr bool kStreamKernel = false;
 template <> inline constexpr bool kStreamKernel<EightSchools<16>> = true;
 template <> inline constexpr bool kStreamKernel<Simple<1>> = true;
 template <> inline constexpr bool kStreamKernel<SV<64>> = true;
+template <> inline constexpr bool kStreamKernel<SVNcp<64>> = true;
 template <> inline constexpr bool kStreamKernel<Logistic<16>> = true;
 template <> inline constexpr bool kStreamKernel<Radon<64>> = true;
 #endif
@@ -1239,7 +1247,8 @@ int exmc_hip_model_create(int kind, int d, const double* data, int n_data, int d
       m->sp.tiny32 = f32r(1.0e-30);
       break;
     }
-    case EXMC_MODEL_SV: {
+    case EXMC_MODEL_SV:
+    case EXMC_MODEL_SV_NCP: {   // the same data and constants; SVNcp<64> reads SV's
       if (n_data != 100 || !data) { delete m; return fail(EXMC_ERR_BADARG, "sv is compiled for T = 100 returns"); }
       m->d = 102;
       static const double lanczos[9] = {0.99999999999980993,  676.5203681218851,     -1259.1392167224028,
@@ -1469,6 +1478,7 @@ int exmc_hip_model_default_dense_lanes(const exmc_hip_model* m) {
   if (!m) return -1;
   switch (m->kind) {
     case EXMC_MODEL_SV: return 64;
+    case EXMC_MODEL_SV_NCP: return 64;
     case EXMC_MODEL_RADON: return 64;
     case EXMC_MODEL_LOGISTIC: return 16;
     default: return 1;

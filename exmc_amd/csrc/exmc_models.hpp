@@ -582,6 +582,125 @@ struct SV : ModelDefaults {
 };
 
 // ------------------------------------------------------------------------------------------
+// stochastic volatility, non-centred (EXMC_MODEL_SV_NCP): what the reference's compiler makes of sv
+// with ncp: true. Its pass rewrites a Normal whose mu AND sigma are references
+// (rewrite/non_centered_parameterization.ex:50-55): s_1 ~ N(0.0, sigma) stays centred, s_t ~
+// N(s_{t-1}, sigma) becomes z_t ~ N(0, 1) with s_t = s_{t-1} + sigma z_t (compiler.ex:444-463).
+// Kernel order: dims 0 = s_1, 1..T-1 = z_2..z_T, T = log sigma, T+1 = log nu; same data, constants
+// and launch settings as SV<64>. The walk is a wave-wide prefix scan of x = (s_1, sigma z_2, ...),
+// its adjoint A_t = sum_{u >= t} dL/ds_u a suffix scan (exmc_device.hpp wave_scan_fwd / _bwd; the
+// lanes past T hold 0.0). Gradient: d/ds_1 = A_1 + dN(s_1)/ds_1, d/dz_t = -z_t + sigma A_t, and
+// d/dlog sigma from the sum of (e_1^2 - 1) and x_t A_t -- the centred form's E2 sum -- plus the prior.
+// ------------------------------------------------------------------------------------------
+template <int G>
+struct SVNcp : SV<G> {
+  static_assert(G == 64, "the non-centred sv is compiled for one chain per wavefront");
+  using B = SV<G>;
+  using Consts = typename B::Consts;
+  using Lane = typename B::Lane;
+  using MM = typename B::MM;
+  static constexpr int T = B::T, D = B::D, DPL = B::DPL;
+
+  __device__ static __forceinline__ double logp_grad(const Consts& c, const Lane& ln, int l,
+                                                     const double (&q)[DPL], double (&g)[DPL]) {
+    return with_fast_div([&](auto& dv) -> double { return eval(c, ln, l, q, g, dv); });
+  }
+
+  // Quotients as in SV: sigma and nu watched in [2^-100, 2^100); s_1 (the one residual) and each
+  // z^2 watched in 2^+-250; every walk value s_t in [2^-380, 2^7) for the short exp(-s_t).
+  template <class DV>
+  __device__ static __forceinline__ double eval(const Consts&, const Lane& ln, int l,
+                                                const double (&q)[DPL], double (&g)[DPL], DV& dv) {
+    const double zs_raw = group_bcast_c<G, T % G>(q[T / G]);
+    const double zn_raw = group_bcast_c<G, (T + 1) % G>(q[(T + 1) / G]);
+    constexpr bool kFast = std::is_same_v<DV, Div<true>>;
+    const double zs = clamp200(zs_raw), zn = clamp200(zn_raw);
+    double ez[2] = {zs, zn};
+    lane_batch<G, 2>(ez, l, [](double v) { return MM::exp_pm200(v); });   // clamp200'ed: always in range
+    const double sigma = ez[0], nu = ez[1];
+    const double ss = fmax(sigma, ln.k[B::kTiny]);
+    const double sdf = fmax(nu, ln.k[B::kTiny]);
+    dv.template watch_exp_if<-100, 100>(true, ss);
+    dv.template watch_exp_if<-100, 100>(true, sdf);
+    const Recip rss = make_recip(ss), rsdf = make_recip(sdf);
+    const double t_sigma = (ln.k[B::kLogLamS] - ln.k[B::kLamS] * sigma) + zs;
+    const double t_nu = (ln.k[B::kLogLamN] - ln.k[B::kLamN] * nu) + zn;
+    const double hp1 = (sdf + 1.0) / 2.0, h = sdf / 2.0;
+    double d1, d0, lg1, lg0;
+    double lx[2] = {sdf * ln.k[B::kPi], ss};   // in: arguments, out: their logarithms
+    lanczos_pair_d<MM, G>(ln.k[B::kLz0], ln.k[B::kHalfLog2Pi], l, ln.lzc, ln.lzj,
+                          hp1, h, lx, lg1, d1, lg0, d0, dv);
+    const double An = (lg1 - lg0) - 0.5 * lx[0];
+    const double dAn = (0.5 * d1 - 0.5 * d0) - dv(0.5, rsdf);
+    const double cn = ln.k[B::kLog2Pi] + 2.0 * lx[1];   // Normal(s_1; 0, sigma)
+    const double c1 = ln.k[B::kLog2Pi] + 2.0 * 0.0;     // Normal(z_t; 0, 1): log(1.0) = 0
+    // s_1's own term: e_1 = (s_1 - 0.0) / sigma on lane 0 (the other lanes' value is unused)
+    const double resid = q[0] - 0.0;
+    dv.template watch_exp_if<-250, 250>(l == 0, resid);
+    const double e1 = dv(resid, rss);
+    // the walk: x = (s_1, sigma z_2, ..., sigma z_T, 0, ...), s = its prefix sums
+    double x[DPL], s[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      const int i = l + k * G;
+      x[k] = (i == 0) ? q[k] : ((i < T) ? sigma * q[k] : 0.0);
+      s[k] = x[k];
+    }
+    wave_scan_fwd(s);
+    double P[DPL], LL[DPL], DN[DPL], a[DPL];
+    bool valid[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      const int i = l + k * G;
+      valid[k] = i < D;
+      const bool ist = i < T;
+      const double si = s[k];
+      // the two specials in their short forms inside the fast window, as in SV
+      dv.template watch_exp_if<-380, 7>(ist, si);
+      const double z = ln.r[k] * (kFast ? MM::exp_pm200(-si) : MM::exp(-si));
+      const double zz = z * z;
+      dv.template watch_exp_if<-250, 250>(ist, zz);
+      const double w = dv(zz, rsdf);
+      const double lg = kFast ? MM::log_ge1(1.0 + w) : MM::log(1.0 + w);
+      const double wr = dv(w, 1.0 + w);
+      const double qk = q[k];
+      P[k] = ist ? ((i == 0) ? (-0.5 * (e1 * e1 + cn)) : (-0.5 * (qk * qk + c1))) : 0.0;
+      LL[k] = ist ? ((An - si) - hp1 * lg) : 0.0;
+      DN[k] = ist ? ((dAn - 0.5 * lg) + dv(hp1 * wr, rsdf)) : 0.0;
+      a[k] = ist ? (-1.0 + (sdf + 1.0) * wr) : 0.0;   // dL/ds_t
+    }
+    wave_scan_bwd(a);   // a = A_t
+    const double de1 = -dv(e1, rss);
+    double s4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      const int i = l + k * G;
+      const bool ist = i < T;
+      const double ZA = ist ? ((i == 0) ? (e1 * e1 - 1.0) : (x[k] * a[k])) : 0.0;
+      g[k] = (i == 0) ? (a[k] + de1) : ((-q[k]) + sigma * a[k]);
+      // the four sums as ONE reduce-scatter, as in SV
+      s4[0] = valid[k] ? (s4[0] + P[k]) : s4[0];
+      s4[1] = valid[k] ? (s4[1] + LL[k]) : s4[1];
+      s4[2] = valid[k] ? (s4[2] + ZA) : s4[2];
+      s4[3] = valid[k] ? (s4[3] + DN[k]) : s4[3];
+    }
+    rs64_allsum4(s4);
+    const double sp = s4[0], sl = s4[1], sz = s4[2], sn = s4[3];
+    const bool in_s = (zs_raw > -200.0) && (zs_raw < 200.0);
+    const bool in_n = (zn_raw > -200.0) && (zn_raw < 200.0);
+    const double g_s = in_s ? ((sz - ln.k[B::kLamS] * sigma) + 1.0) : 0.0;
+    const double g_n = in_n ? ((sn * nu - ln.k[B::kLamN] * nu) + 1.0) : 0.0;
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      const int i = l + k * G;
+      if (i == T) g[k] = g_s;
+      if (i == T + 1) g[k] = g_n;
+    }
+    return ((t_sigma + t_nu) + sp) + sl;
+  }
+};
+
+// ------------------------------------------------------------------------------------------
 // logistic regression, K = 20 covariates, N observations (STANDARD_BENCHMARKS.md:41-49;
 // Bernoulli clip dist/bernoulli.ex:17-27). dims: 0 alpha, 1..20 beta_j. Observation n is
 // handled by lane n mod G of the chain's group (row n of X stays in registers for both the

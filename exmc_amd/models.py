@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 STD_NORMAL, SIMPLE, EIGHT_SCHOOLS, SV, LOGISTIC, RADON = range(6)
+SV_NCP = 7   # 6 is EXMC_MODEL_CUSTOM (a generated model, exmc_amd/codegen.py)
 
 EIGHT_SCHOOLS_Y = [28.0, 8.0, -3.0, 7.0, -1.0, 1.0, 18.0, 12.0]
 EIGHT_SCHOOLS_SIGMA = [15.0, 10.0, 16.0, 11.0, 9.0, 11.0, 10.0, 18.0]
@@ -17,8 +18,37 @@ EIGHT_SCHOOLS_SIGMA = [15.0, 10.0, 16.0, 11.0, 9.0, 11.0, 10.0, 18.0]
 SIMPLE_Y = [float(np.float32(v)) for v in (2.1, 1.8, 2.5, 2.0, 1.9, 2.3, 2.2, 1.7, 2.4, 2.6)]
 
 
+def invert_ncp_init(vals, ncp_info):
+    """invert_ncp_init (sampler.ex:362-388): the user gives constrained values; a non-centred id's
+    free variable is z = (x - mu) / sigma, with mu and sigma resolved from the ORIGINAL init values
+    (an id missing from vals is left alone). vals: name -> float; returns the updated copy."""
+    res = lambda s: vals[s] if isinstance(s, str) else float(s)   # noqa: E731
+    raw = {id_: (vals[id_] - res(src["mu"])) / res(src["sigma"])
+           for id_, src in ncp_info.items() if id_ in vals}
+    out = dict(vals)
+    out.update(raw)
+    return out
+
+
+def reconstruct_ncp(x, var_names, ncp_info):
+    """reconstruct_ncp (sampler.ex:1300-1313): x = mu + sigma * z in topological order, in place on
+    the constrained draws x [..., d] (an id's references are reconstructed before it)."""
+    idx = {n: i for i, n in enumerate(var_names)}
+    pending = dict(ncp_info)
+    while pending:
+        ready = [i for i, s in pending.items()
+                 if all(not (isinstance(v, str) and v in pending) for v in s.values())]
+        if not ready:
+            raise ValueError("cyclic non-centred references")
+        for id_ in ready:
+            s = pending.pop(id_)
+            val = lambda v: x[..., idx[v]] if isinstance(v, str) else float(v)   # noqa: E731
+            x[..., idx[id_]] = val(s["mu"]) + val(s["sigma"]) * x[..., idx[id_]]
+    return x
+
+
 class ModelSpec:
-    def __init__(self, kind, name, data, var_names, transforms, default_init=None):
+    def __init__(self, kind, name, data, var_names, transforms, default_init=None, ncp_info=None):
         self.kind = kind
         self.name = name
         self.data = np.ascontiguousarray(np.asarray(data, dtype=np.float64))
@@ -26,6 +56,9 @@ class ModelSpec:
         self.transforms = dict(transforms)        # var name -> "log" | None
         self.d = len(self.var_names)
         self.default_init = default_init
+        # id -> {"mu": ref | number, "sigma": ref | number}: the free variable of id is z, the value
+        # mu + sigma z (Compiler.compile_for_sampling's ncp_info); empty for a centred kind
+        self.ncp_info = dict(ncp_info or {})
 
     # reference flat layout = ids sorted as strings (point_map.ex:37)
     def flat_order(self):
@@ -34,6 +67,8 @@ class ModelSpec:
     def to_unconstrained(self, init_values):
         """PointMap.to_unconstrained + pack (sampler.ex:351-356); missing names are an error, as
         Map.fetch! is in the reference."""
+        if self.ncp_info:
+            init_values = invert_ncp_init({k: float(v) for k, v in init_values.items()}, self.ncp_info)
         q = np.zeros(self.d)
         for i, name in enumerate(self.var_names):
             x = float(init_values[name])
@@ -41,11 +76,14 @@ class ModelSpec:
         return q
 
     def constrain(self, q):
-        """Transform.apply per entry (transform.ex:15-29): q [..., d] -> constrained."""
+        """Transform.apply per entry (transform.ex:15-29): q [..., d] -> constrained; then, for a
+        non-centred kind, reconstruct_ncp (build_trace, sampler.ex:1281-1313)."""
         x = np.array(q, dtype=np.float64, copy=True)
         for i, name in enumerate(self.var_names):
             if self.transforms.get(name) == "log":
                 x[..., i] = np.exp(np.clip(x[..., i], -200.0, 200.0))
+        if self.ncp_info:
+            reconstruct_ncp(x, self.var_names, self.ncp_info)
         return x
 
 
@@ -207,3 +245,17 @@ def sv(returns):
     init["sigma"] = 0.1
     init["nu"] = 10.0
     return ModelSpec(SV, "sv", r, names, {"sigma": "log", "nu": "log"}, init)
+
+
+def sv_ncp(returns):
+    """Stochastic volatility as the reference samples it by default: Sampler.sample/3 compiles with
+    ncp: true (sampler.ex:33-37), and the non-centring pass rewrites every free Normal whose mu and
+    sigma are both references (non_centered_parameterization.ex:50-55) -- s_2..s_T, not s_1, whose
+    mu is the literal 0.0. Same data, names, kernel order and default init as `sv`; the free
+    variables of s_2..s_T are z_t ~ N(0, 1) with s_t = s_{t-1} + sigma z_t (EXMC_MODEL_SV_NCP).
+    to_unconstrained inverts an init of s_t values, constrain reconstructs the walk, so draws and
+    traces speak of s_t as for `sv`."""
+    spec = sv(returns)
+    ncp = {"s_%d" % t: {"mu": "s_%d" % (t - 1), "sigma": "sigma"} for t in range(2, 101)}
+    return ModelSpec(SV_NCP, "sv_ncp", spec.data, spec.var_names, spec.transforms,
+                     spec.default_init, ncp_info=ncp)

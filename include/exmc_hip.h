@@ -58,7 +58,11 @@ enum {
   EXMC_MODEL_RADON = 5,
   /* a model generated from Builder IR (compiler.ex:46-58 -> exmc_amd/codegen.py); present only
    * in a plug-in build of this library made for that model; data = the generator's data vector */
-  EXMC_MODEL_CUSTOM = 6
+  EXMC_MODEL_CUSTOM = 6,
+  /* sv as the reference compiles it with ncp: true (its default): data r[100] like SV, kernel
+   * order s_1, z_2..z_100, log sigma, log nu (s_t = s_{t-1} + sigma z_t);
+   * 64 lanes per chain only */
+  EXMC_MODEL_SV_NCP = 7
 };
 
 typedef struct exmc_hip_model exmc_hip_model;
@@ -98,7 +102,7 @@ int exmc_hip_device_count(void);
 
 /* Replaces Compiler.compile_for_sampling/2 for the built-in model kinds
  * (lib/exmc/compiler.ex:46-58): uploads model data, prepares per-model constants.
- * `data`/`n_data` per kind: EIGHT_SCHOOLS y[8],sigma[8]; SIMPLE y[n]; SV r[100];
+ * `data`/`n_data` per kind: EIGHT_SCHOOLS y[8],sigma[8]; SIMPLE y[n]; SV and SV_NCP r[100];
  * LOGISTIC X[N][20] row-major then y[N]; RADON u[85], county_start[86], floor[N], y[N] with the
  * observations sorted by county, N <= 1024 (EXMC_ERR_UNSUPPORTED above: the 64-lane layout gives a
  * lane 16 observation slots). Free variables are in "kernel order" (DESIGN.md section 2). */
