@@ -912,12 +912,14 @@ def _apply_ncp(ir, ncp):
     return nodes, info
 
 
-def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, waves_per_simd=1):
+def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, waves_per_simd=1, scan=True):
     """Compiler.compile_for_sampling (compiler.ex:46-58) as source text. `rewrite_passes` runs the
     reference's IR passes first (`rewrite`); without it the IR is taken as already rewritten
     (transforms explicit), which is what an exporter on the Elixir side sends. `lanes` = 16 / 32 /
     64 asks for the lane layout of codegen_lanes.py (a chain over that many lanes, several
-    dimensions per lane); models above MAX_D free dimensions get it by themselves.
+    dimensions per lane); models above MAX_D free dimensions get it by themselves. `scan`: the
+    64-lane layout evaluates the random walks the non-centred rewrite makes as wave-wide scans
+    (codegen_lanes.py, scan chains); False keeps them unrolled, the text of earlier versions.
 
     Term order: Map.values of the node map (compiler.ex:176-180) = ids sorted as strings for up to
     MAX_NODES_SORTED nodes. A larger Erlang map iterates in the order of its internal hash, which
@@ -957,6 +959,7 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
     one_lane = len(flat_names) <= MAX_D
     g = _Graph()
     custom_roots = set()      # terms that are the result of a Custom closure (a hand-written reduction)
+    ncp_nodes = {}            # non-centred id -> its node mu + sigma * z (the lane layout's scan chains)
 
     def resolve_ref(id_, stack=()):
         # compiler.ex:447-463
@@ -971,7 +974,8 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
         if id_ in ncp_info:
             mu = resolve_value(ncp_info[id_]["mu"], stack + (id_,))
             sigma = resolve_value(ncp_info[id_]["sigma"], stack + (id_,))
-            return g.add(mu, g.mul(sigma, z))
+            ncp_nodes[id_] = g.add(mu, g.mul(sigma, z))
+            return ncp_nodes[id_]
         return _apply_transform(g, nodes[id_]["transform"], z)
 
     def resolve_value(v, stack=()):
@@ -1264,13 +1268,15 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
     if lanes is not None:
         # several dimensions per lane (codegen_lanes.py): any d, the repeated terms over the lanes
         from . import codegen_lanes
-        out.lane_layout = codegen_lanes.generate(g, terms, custom_roots, out.d, lanes, waves_per_simd)
+        walks = codegen_lanes.find_chains(g, ncp_info, ncp_nodes) if scan else []
+        out.lane_layout = codegen_lanes.generate(g, terms, custom_roots, out.d, lanes, waves_per_simd, walks)
         # (the lane function is a section of its own that its users include once per table placement)
         out.header = "#ifndef EXMC_GEN_LANES_SECTION\n" + out.header + \
                      "\n#define EXMC_GEN_LOFF %d   /* where the lane layout's table starts in data */\n" \
                      % out.data.size + out.lane_layout["text"]
         out.data = np.concatenate([out.data, out.lane_layout["data"]])
         out.lanes = lanes
+    out.scan_chains = out.lane_layout["scan_chains"] if out.lane_layout is not None else []
     out.digest = hashlib.sha256(out.header.encode()).hexdigest()[:16]
     out.n_ops = out.header.count("\n")
     return out
@@ -1678,10 +1684,11 @@ class GeneratedSpec(ModelSpec):
 
 
 def compile_ir(ir, ncp=True, name="generated", default_init=None, verbose=False, rewrite_passes=False,
-               lanes=None, waves_per_simd=1):
+               lanes=None, waves_per_simd=1, scan=True):
     """IR -> GeneratedSpec with its plug-in library built. Needs hipcc (no fallback). `lanes`,
-    `waves_per_simd`: see `generate` / codegen_lanes.generate."""
-    gen = generate(ir, ncp=ncp, rewrite_passes=rewrite_passes, lanes=lanes, waves_per_simd=waves_per_simd)
+    `waves_per_simd`, `scan`: see `generate` / codegen_lanes.generate."""
+    gen = generate(ir, ncp=ncp, rewrite_passes=rewrite_passes, lanes=lanes, waves_per_simd=waves_per_simd,
+                   scan=scan)
     so = build_plugin(gen, verbose=verbose)
     return GeneratedSpec(gen, so, name=name, default_init=default_init)
 
@@ -1691,7 +1698,8 @@ def compile_ir(ir, ncp=True, name="generated", default_init=None, verbose=False,
 #   model.json: {"ncp": true, "nodes": {"mu": {"op": "rv", "dist": "normal",
 #                "params": {"mu": 0.0, "sigma": 5.0}, "transform": null}, ...,
 #                "y_obs": {"op": "obs", "target": "y", "value": [2.1, 1.8]}}}
-#   ("rewrite": true runs the reference's IR passes first; obs nodes take reduce / weight / mask /
+#   ("rewrite": true runs the reference's IR passes first; "scan": false keeps the random walks of
+#   the 64-lane layout unrolled (codegen_lanes.py, scan chains); obs nodes take reduce / weight / mask /
 #   censored / likelihood, {"op": "det", "fun": "affine", "args": [a, b, "x"]} and
 #   {"op": "meas_obs", "target": "x", "value": [...], "info": ["affine", a, b]} are accepted)
 #   out_dir gets exmc_gen_model.h, libexmc_hip_gen.so and model.json (d, var_names = the flat
@@ -1729,12 +1737,13 @@ def main(argv=None):
         raise SystemExit("usage: python -m exmc_amd.codegen model.json out_dir [--no-build]")
     doc = json.load(open(argv[0]))
     gen = generate(ir_from_json(doc), ncp=doc.get("ncp", True), rewrite_passes=doc.get("rewrite", False),
-                   lanes=doc.get("lanes"), waves_per_simd=doc.get("waves_per_simd", 1))
+                   lanes=doc.get("lanes"), waves_per_simd=doc.get("waves_per_simd", 1), scan=doc.get("scan", True))
     os.makedirs(argv[1], exist_ok=True)
     with open(os.path.join(argv[1], "exmc_gen_model.h"), "w") as f:
         f.write(gen.header)
     meta = dict(kind=CUSTOM, d=gen.d, var_names=gen.var_names, transforms=gen.transforms,
-                ncp_info=gen.ncp_info, data=gen.data.tolist(), digest=gen.digest, lanes_per_chain=gen.lanes)
+                ncp_info=gen.ncp_info, data=gen.data.tolist(), digest=gen.digest, lanes_per_chain=gen.lanes,
+                scan=bool(doc.get("scan", True)), scan_chains=gen.scan_chains)
     if "--no-build" not in argv:
         shutil.copyfile(build_plugin(gen), os.path.join(argv[1], "libexmc_hip_gen.so"))
         meta["library"] = "libexmc_hip_gen.so"

@@ -50,6 +50,25 @@ What keeps the generated kernels near the hand-written ones (DESIGN.md section 4
     adds the groups' sums in group order.
   * waves_per_simd = 2 (generate): the register cap of two resident waves, with the plug-in's LDS
     sized so that eight workgroups fit a CU (exmc_models.hpp EXMC_GEN_LDS_*).
+  * Scan chains (find_chains, 64 lanes only): the non-centred rewrite turns a random walk of chained
+    Normals into n_k = n_{k-1} + sigma z_k, which resolves to a serial chain of fused multiply-adds
+    that every lane evaluated, with its adjoint. A chain is a maximal path h -> n_1 -> ... -> n_m of
+    non-centred nodes with mu(n_k) = n_{k-1} and one common sigma reference, every n_k but the last
+    the mu of exactly one non-centred node (a node that is the mu of several, or whose successor has
+    another sigma, ends the chain; the next ones start chains of their own with it as head). It is
+    evaluated as a wave-wide prefix sum of (h, sigma z_1, ..., sigma z_m), element e in slot e / 64
+    of lane e % 64 (EXMC_GEN_SCAN_FWD: exmc_device.hpp wave_scan_fwd), published in an extension of
+    the LDS strip, from which the families gather n_k like a position entry; its adjoint is the suffix
+    sum A_e of the owner sums of the families' cells (EXMC_GEN_SCAN_BWD: wave_scan_bwd), and
+    d/dz_e += sigma A_e (a strip cell the owner of z_e adds), d/dsigma += sum_e z_e A_e (per lane
+    over its slots, then the butterfly), d/dh += A_0 seed the uniform part's gradient. A chain is
+    scanned when it has at least MIN_SCAN increments and its m + 1 elements fit the DPL slots; and
+    the uniform part must not read its walk values (it runs before the forward scans and after the
+    backward ones): a chain whose values a head, a sigma or a lone term reads keeps the unrolled
+    text, and the others are tried again without it. scan=False (codegen.generate) keeps every walk
+    unrolled, the text of earlier versions byte for byte. The generated text carries a host
+    statement of both macros (include/exmc_scan.h, the whole chain from the strip alone), which the
+    host checker runs where the device runs the scans.
 
 Numeric contract: the lane contract of DESIGN.md section 2 -- per lane left to right over its slots,
 then the xor butterfly over the group -- so the sum of a family's terms is NOT the reference's
@@ -57,7 +76,10 @@ left-to-right Nx.sum (nor, for models above 32 nodes, the hash order of an Erlan
 restated: terms are taken in sorted-id order); the difference is rounding of a sum (a few ulp of
 the log-density). The host checker (tests/gen_checker.py) runs the same text over G virtual lanes
 in that order and the GPU equals it bit for bit; against the hand-written models of the oracle the
-generated log-density and gradient agree to 1e-12 relative.
+generated log-density and gradient agree to 1e-12 relative. A scan chain's walk and adjoint are
+summed in the scans' order (in-row Hillis-Steele, the two cross-row stages, the slot carry: the
+order of the hand-written sv_ncp kind), not in sequence; every stage selects, and elements past
+the walk are 0.0 by a select, never by a multiplication.
 """
 import math
 
@@ -66,6 +88,7 @@ import numpy as np
 from . import codegen as cg
 
 MIN_FAMILY = 4          # fewer units than this are evaluated by every lane (the uniform part)
+MIN_SCAN = 16           # increments of a scan chain: a shorter walk keeps the unrolled text
 # doubles of table rows / gathered variables fetched ahead per lane (emit_family), by resident waves
 # per SIMD: a lone wave has 512 registers and nobody to hide its latency, a pair 256 each
 PAIR_MIN_COLS = 8      # families of at least this many per-unit columns store them in interleaved pairs (generate)
@@ -92,7 +115,7 @@ class _LGraph(cg._Graph):
         return i
 
 
-_LEAVES = ("lit", "data", "q", "ext", "uc", "col", "gat", "red", "wred")
+_LEAVES = ("lit", "data", "q", "ext", "uc", "col", "gat", "red", "wred", "scn")
 
 
 def _np_eval(g, nodes, leaf):
@@ -486,17 +509,162 @@ def plan(g, term_roots, custom_roots, D, G):
     return families, scalar_units
 
 
-def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
+class _Chain:
+    pass
+
+
+def find_chains(g, ncp_info, ncp_nodes):
+    """The scan chains of a model: maximal paths h -> n_1 -> ... -> n_m of non-centred nodes
+    (n_k = n_{k-1} + sigma z_k after the rewrite) where mu(n_k) = n_{k-1}, all n_k share ONE sigma
+    reference, and every n_k but the last is the mu of exactly one non-centred node (its successor).
+    A node that is the mu of several non-centred nodes ends its chain, and each of those starts a
+    chain of its own whose head is that node; so does a node whose sigma differs from its mu's.
+    Only resolved nodes count (a walk's tail that nothing reads is not in the graph). The head h
+    (mu of n_1) is any resolved value. -> [_Chain], in the order of their first ids."""
+    kids = {}
+    for c in sorted(ncp_nodes):
+        kids.setdefault(ncp_info[c]["mu"], []).append(c)
+
+    def succ(p):
+        ks = kids.get(p, [])
+        return ks[0] if (len(ks) == 1 and ncp_info[ks[0]]["sigma"] == ncp_info[p]["sigma"]) else None
+    starts = [c for c in sorted(ncp_nodes)
+              if not (ncp_info[c]["mu"] in ncp_nodes and succ(ncp_info[c]["mu"]) == c)]
+    out = []
+    for c0 in starts:
+        ids = [c0]
+        while succ(ids[-1]) is not None:
+            ids.append(succ(ids[-1]))
+        ch = _Chain()
+        ch.ids, ch.nodes = ids, [ncp_nodes[i] for i in ids]
+        ch.head_id, ch.sigma_id = ncp_info[c0]["mu"], ncp_info[c0]["sigma"]
+        op = g.ops[ch.nodes[0]]
+        ch.head = op[1]
+        ch.sigma = g.ops[op[2]][1]
+        ch.z = []
+        prev, ok = ch.head, True
+        for n in ch.nodes:                     # n = add(prev, mul(sigma, q z)), as resolve_ref builds it
+            op = g.ops[n]
+            m = g.ops[op[2]] if op[0] == "add" else None
+            ok = ok and op[1] == prev and m is not None and m[0] == "mul" and m[1] == ch.sigma \
+                and g.ops[m[2]][0] == "q"
+            if not ok:
+                break
+            ch.z.append(g.ops[m[2]][1])
+            prev = n
+        if ok:
+            ch.m = len(ids)
+            out.append(ch)
+    return out
+
+
+class _SGraph(cg._Graph):
+    """The graph of a layout with scan chains: `scn j` is a run-time value of the scans (the
+    sigma reduction and A_0 of chain j // 2) that the differentiation does not look into."""
+    LEAF_CONST = dict(cg._Graph.LEAF_CONST, scn=False, wred=False)
+
+
+def _with_walk_leaves(g, leaf_of):
+    """A copy of g where each walk node n (leaf_of[n] = its strip index) is a position-like leaf
+    `q`: its value is read from the chain's strip like a position entry. Node indices are kept,
+    so the terms, the registered sums and every other node stay what they are."""
+    h = _SGraph()
+    h.ops, h.const, h.key = list(g.ops), list(g.const), dict(g.key)
+    h.data, h.f32, h.sums = list(g.data), set(g.f32), {k: list(v) for k, v in g.sums.items()}
+    for n, i in leaf_of.items():
+        del h.key[h.ops[n]]
+        h.ops[n] = ("q", i)
+        h.key[h.ops[n]] = n
+        h.const[n] = False
+    return h
+
+
+class _WalkRead(Exception):
+    """The uniform part reads a walk value of these chains (a head or a scale that is a step of
+    another walk, a lone term of a step): they keep the unrolled text."""
+
+    def __init__(self, chains):
+        Exception.__init__(self)
+        self.chains = chains
+
+
+def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1, chains=()):
     """-> dict(text, data, lanes, dpl, ...) for the lane layout. waves_per_simd: resident waves per
     SIMD the sampling kernel's register allocation must allow (ModelDefaults::kNutsWavesPerSimd):
     1 leaves the allocator the whole file; 2 caps it at 256 vector registers, which can pay when a
     launch has more wavefronts than the chip has SIMDs (chains x lanes / 64 > 1024) -- it does for
     the hand-written sv and logistic kinds, it does not for their generated forms, whose bodies
-    then spill inside the leaf loop (profiles/r3_gen)."""
+    then spill inside the leaf loop (profiles/r3_gen). chains: find_chains of the model; those that
+    qualify (module docstring, scan chains) are evaluated as wave-wide scans."""
     if waves_per_simd not in (1, 2):
         raise cg.CodegenError("waves_per_simd must be 1 or 2")
     if G not in (16, 32, 64):
         raise cg.CodegenError("lanes per chain must be 16, 32 or 64")
+    DPL = (D + G - 1) // G
+    use = [c for c in chains if G == 64 and c.m >= MIN_SCAN and (c.m + 1 + 63) // 64 <= DPL]
+    while use:
+        base, leaf_of = D + 1, {}
+        for c in use:                          # strip: [position][0.0][walks][walk adjoints][...]
+            c.N, c.w0 = (c.m + 64) // 64, base
+            leaf_of.update((n, c.w0 + 1 + k) for k, n in enumerate(c.nodes))
+            base += c.m + 1
+        for c in use:
+            c.ga0 = base
+            base += c.m + 1
+        try:
+            return _generate(_with_walk_leaves(g, leaf_of), term_roots, custom_roots, D, G, waves_per_simd,
+                             use, base)
+        except _WalkRead as e:
+            use = [c for c in use if c not in e.chains]
+    return _generate(g, term_roots, custom_roots, D, G, waves_per_simd, [], D + 1)
+
+
+def _scan_host_defaults(chains):
+    """The scans of the generated text as host C (tests/gen_checker.py runs the lane function lane
+    after lane, so no lane sees another's registers): each macro computes the whole chain from the
+    LDS strip alone, in the device's association order (include/exmc_scan.h), and writes every
+    element. The device defines them first (exmc_models.hpp: wave_scan_fwd / wave_scan_bwd)."""
+    return [
+        "/* scan chains (codegen_lanes.py): %d; their host statement unless the includer defines the scans */" % len(chains),
+        "#ifndef EXMC_GEN_SCAN_FWD",
+        '#include "exmc_scan.h"',
+        "#define EXMC_GEN_SCAN_FWD(N, v, m, zo, h, sg, wo) do { \\",
+        "    double e_[64 * (N)]; \\",
+        "    for (int i_ = 0; i_ < 64 * (N); i_++) \\",
+        "      e_[i_] = (i_ == 0) ? (h) : ((i_ <= (m)) ? (sg) * EXMC_GEN_SH(EXMC_GEN_IT((zo) + i_)) : 0.0); \\",
+        "    exmc_scan_fwd64(e_, (N)); \\",
+        "    for (int i_ = 0; i_ <= (m); i_++) EXMC_GEN_SH((wo) + i_) = e_[i_]; \\",
+        "    (void)(v); } while (0)",
+        "#endif",
+        "#ifndef EXMC_GEN_SCAN_BWD",
+        "#define EXMC_GEN_SCAN_BWD(N, v, m, zo, sg, we, ww, ga, sz, a0) do { \\",
+        "    double e_[64 * (N)], p_[64]; \\",
+        "    const int* el_ = (const int*)lt + EXMC_GEN_ELL_OFF; \\",
+        "    for (int i_ = 0; i_ < 64 * (N); i_++) { \\",
+        "      double acc_ = 0.0; \\",
+        "      for (int j_ = 0; j_ < (ww); j_++) \\",
+        "        acc_ = acc_ + EXMC_GEN_SH(el_[(i_ & 63) * EXMC_GEN_NELL + (we) + (i_ >> 6) * (ww) + j_]); \\",
+        "      e_[i_] = acc_; \\",
+        "    } \\",
+        "    exmc_scan_bwd64(e_, (N)); \\",
+        "    for (int i_ = 1; i_ <= (m); i_++) EXMC_GEN_SH((ga) + i_) = (sg) * e_[i_]; \\",
+        "    for (int l_ = 0; l_ < 64; l_++) { \\",
+        "      double q_ = 0.0; \\",
+        "      for (int k_ = 0; k_ < (N); k_++) { \\",
+        "        const int i_ = l_ + 64 * k_; \\",
+        "        q_ = (i_ >= 1 && i_ <= (m)) ? q_ + EXMC_GEN_SH(EXMC_GEN_IT((zo) + i_)) * e_[i_] : q_; \\",
+        "      } \\",
+        "      p_[l_] = q_; \\",
+        "    } \\",
+        "    (sz) = exmc_allsum64(p_); \\",
+        "    (a0) = e_[0]; \\",
+        "    (void)(v); } while (0)",
+        "#endif",
+        "",
+    ]
+
+
+def _generate(g, term_roots, custom_roots, D, G, waves_per_simd, chains, sh_base):
     DPL = (D + G - 1) // G
     families, scalar_units = plan(g, term_roots, custom_roots, D, G)
     # ---- uniform constants: one table for the uniform part and every template ----
@@ -514,7 +682,7 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
     # ---- templates ----
     boundary = []            # distinct uniform dynamic nodes read by templates, in first-use order
     b_index = {}
-    sh_off = D + 1           # LDS strip: [q (D)] [zero cell] [adjoint strips ...]
+    sh_off = sh_base         # LDS strip: [q (D)] [zero cell] [walks, walk adjoints] [adjoint strips ...]
     dcols, icols = [], []    # table columns (each NPAD long), in emission order
     def build_template(f):
         """Twice: the second time the quotients by a denominator whose reciprocal the first pass
@@ -778,6 +946,8 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
             cpart = cpart + np.float64(g_const_value(c))
         f.cpart = float(cpart)
     n_split = len(g.ops)
+    for ci, c in enumerate(chains):            # the scans' run-time values: sum_e z_e A_e and A_0
+        c.sz, c.a0 = g._node("scn", 2 * ci), g._node("scn", 2 * ci + 1)
     # reduced values: s[0] = log-density of the families, s[1 + j] = adjoint of boundary node j
     acc_of = {}
     for f in families:
@@ -791,7 +961,7 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
     # hundred vector registers in the sampling kernel). Tangents d node / d shared variable are
     # computed next to the values instead; what stays live is the Jacobian of the boundary nodes:
     #   d logp / d q_i = d scalar_lp / d q_i + sum_j red_j * d b_j / d q_i
-    fwd_roots = [scalar_lp] + list(boundary)
+    fwd_roots = [scalar_lp] + list(boundary) + [x for c in chains for x in (c.head, c.sigma)]
     spread = {f.out: [(boundary[j], g._node("wred", f.w_of[j])) for j in sorted(f.ext_adj)] for f in ufams}
     tan = _forward_tangents(g, fwd_roots, spread)
     ug = {}
@@ -802,11 +972,16 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
             if tj is not None:
                 term = g.mul(g._node("red", sl_), tj)
                 acc = term if acc is None else g.add(acc, term)
+        for c in chains:                       # d/dsigma += sum_e z_e A_e, d/dhead += A_0
+            for x, tj in ((c.sz, tan.get(c.sigma, {}).get(i)), (c.a0, tan.get(c.head, {}).get(i))):
+                if tj is not None:
+                    term = g.mul(x, tj)
+                    acc = term if acc is None else g.add(acc, term)
         if acc is not None:
             ug[i] = acc
 
     # liveness of the uniform graph
-    outputs = [scalar_lp] + list(ug.values()) + [b for b in boundary]
+    outputs = [scalar_lp] + list(ug.values()) + [b for b in boundary] + [x for c in chains for x in (c.head, c.sigma)]
     live, stack = set(), list(outputs)
     while stack:
         i = stack.pop()
@@ -817,6 +992,11 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
             stack.extend(uf_of[i].inputs)       # its terms are evaluated by the lanes, not here
         elif g.ops[i][0] not in _LEAVES and not g.const[i]:
             stack.extend(g.ops[i][1:])
+    # a walk value is read by the lanes' families only: the uniform part runs before the forward scans
+    # and after the backward ones (module docstring, scan chains)
+    read = [c for c in chains if any(g.ops[i][0] == "q" and c.w0 < g.ops[i][1] <= c.w0 + c.m for i in live)]
+    if read:
+        raise _WalkRead(read)
     for i in sorted(live):
         if g.const[i] and g.ops[i][0] != "lit":
             uc_slot(("node", i), g_const_value(i))
@@ -830,13 +1010,16 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
             after_w.add(i)
 
     # ---- gather lists of the owner lanes (padded to the widest lane per slot) ----
-    contrib = [[] for _ in range(D)]
+    contrib = [[] for _ in range(sh_base)]
     for f in families:
         for p in range(len(f.gather)):
             if f.strip[p] < 0:
                 continue
             for u, var in enumerate(f.gather[p]):
                 contrib[var].append(f.strip[p] + u)
+    for c in chains:                           # d/dz_e += sigma A_e: the cell the backward scan writes
+        for e, var in enumerate(c.z, 1):
+            contrib[var].append(c.ga0 + e)
     width = [0] * DPL
     for i in range(D):
         width[i // G] = max(width[i // G], len(contrib[i]))
@@ -847,12 +1030,21 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
     for k in range(DPL):
         ell_off.append(NELL)
         NELL += width[k]
+    for c in chains:                           # then each walk's elements: [slot k][j < c.W]
+        c.W = max(len(contrib[c.w0 + e]) for e in range(c.m + 1))
+        c.eoff = NELL
+        NELL += c.N * c.W
     ell = []
     for l in range(G):
         for k in range(DPL):
             i = l + k * G
             for j in range(width[k]):
                 ell.append(contrib[i][j] if (i < D and j < len(contrib[i])) else zero_cell)
+        for c in chains:
+            for k in range(c.N):
+                e = l + k * G
+                cells = contrib[c.w0 + e] if e <= c.m else []
+                ell.extend(cells[j] if j < len(cells) else zero_cell for j in range(c.W))
 
     # ---- table layout: [uc][double columns][int32 columns (gather indices, owner lists)] ----
     # Per-unit columns in PAIRS since round 6: columns 2p and 2p + 1 of a family are interleaved over its units
@@ -883,6 +1075,9 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
         for p in range(len(f.gather)):
             col = list(f.gather[p]) + [f.gather[p][0]] * (f.npad - f.n)
             ints.extend(col)
+    for c in chains:                           # the position index of z_e, element e of the scan
+        c.zoff = len(ints)
+        ints.extend([0] + list(c.z) + [0] * (c.N * 64 - c.m - 1))
     ell_base = len(ints)
     ints.extend(ell)
     if len(ints) % 2:
@@ -970,12 +1165,14 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
             return "s[%d]" % op[1]
         if op[0] == "wred":
             return "w[%d]" % op[1]
+        if op[0] == "scn":
+            return "sc%d" % op[1]
         if g.const[i]:
             return "EXMC_GEN_LT(%d)" % uc_of[("node", i)]
         return "u%d" % i
 
     u_nodes = set(i for i in live if not g.const[i] and g.ops[i][0] not in _LEAVES and i not in uf_of)
-    u_pinned = set([scalar_lp] + list(ug.values()) + list(boundary))
+    u_pinned = set([scalar_lp] + list(ug.values()) + list(boundary) + [x for c in chains for x in (c.head, c.sigma)])
     u_plan, u_gone, _ = fuse_plan(g, u_nodes, u_pinned)
 
     # Chain-scalar transcendentals of the uniform part are the same instruction stream whatever their
@@ -1059,6 +1256,8 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
     L.append("")
     L.append("#define EXMC_GEN_IOFF %d   /* the int32 tables start at double EXMC_GEN_IOFF of lt */" % ioff_doubles)
     L.append("")
+    if chains:
+        L.extend(_scan_host_defaults(chains))
     L.append("#else   /* EXMC_GEN_LANES_SECTION: the lane function itself. Included once per table placement")
     L.append("       * with EXMC_GEN_LANES_NAME, EXMC_GEN_LT(i) (double i of the table) and EXMC_GEN_IT(i) (int32 i")
     L.append("       * of its index part) defined by the includer: global memory, or an LDS image of it */")
@@ -1205,6 +1404,17 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
             else:
                 L.append("  const double u%d = w[%d];" % (f.out, f.w0))
         L.extend(ustmts(0, n_split, late=True))
+    for ci, c in enumerate(chains):
+        L.append("  /* scan chain %d: %s .. %s = %s + prefix sums of %s * z (%d increments, %d slots) */"
+                 % (ci, c.ids[0], c.ids[-1], c.head_id, c.sigma_id, c.m, c.N))
+        L.append("  double xw%d[%d];" % (ci, c.N))
+        L.append("  for (int k = 0; k < %d; k++) {" % c.N)
+        L.append("    const int e = l + 64 * k;")
+        L.append("    xw%d[k] = (e == 0) ? %s : ((e <= %d) ? %s * EXMC_GEN_SH(EXMC_GEN_IT(%d + e)) : 0.0);"
+                 % (ci, uref(c.head), c.m, uref(c.sigma), c.zoff))
+        L.append("  }")
+        L.append("  EXMC_GEN_SCAN_FWD(%d, xw%d, %d, %d, %s, %s, %d);"
+                 % (c.N, ci, c.m, c.zoff, uref(c.head), uref(c.sigma), c.w0))
     L.append("  double s[EXMC_GEN_NS];")
     L.append("  for (int j = 0; j < EXMC_GEN_NS; j++) s[j] = 0.0;")
     for fi, f in enumerate(families):
@@ -1213,6 +1423,22 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
         emit_family(f, "family %d" % fi, "s", slots, "hf%d" % fi, split=True)
     L.append("  EXMC_GEN_ALLSUM(s);")
     L.append("  EXMC_GEN_XGROUP(s);   /* EXMC_GEN_NG > 1: the groups' sums, group 0 first */")
+    if chains:
+        L.append("  EXMC_GEN_FENCE();   /* the families' cells of the walk values */")
+    for ci, c in enumerate(chains):
+        L.append("  /* scan chain %d, adjoint: A_e = sum over u >= e of dlogp/ds_u; z_e gets %s * A_e, %s the sum"
+                 % (ci, c.sigma_id, c.sigma_id))
+        L.append("   * of z_e A_e, %s A_0 */" % c.head_id)
+        L.append("  double aw%d[%d];" % (ci, c.N))
+        L.append("  for (int k = 0; k < %d; k++) {" % c.N)
+        L.append("    double acc = 0.0;")
+        if c.W > 0:
+            L.append("    for (int j = 0; j < %d; j++) acc = acc + EXMC_GEN_SH(el[%d + k * %d + j]);" % (c.W, c.eoff, c.W))
+        L.append("    aw%d[k] = acc;" % ci)
+        L.append("  }")
+        L.append("  double sc%d, sc%d;" % (2 * ci, 2 * ci + 1))
+        L.append("  EXMC_GEN_SCAN_BWD(%d, aw%d, %d, %d, %s, %d, %d, %d, sc%d, sc%d);"
+                 % (c.N, ci, c.m, c.zoff, uref(c.sigma), c.eoff, c.W, c.ga0, 2 * ci, 2 * ci + 1))
     L.extend(ustmts(n_split, len(g.ops)))
     L.append("  EXMC_GEN_FENCE();")
     for k in range(DPL):
@@ -1234,7 +1460,9 @@ def generate(g, term_roots, custom_roots, D, G, waves_per_simd=1):
     L.append("}")
     L.append("#endif")
     text = "\n".join(L) + "\n"
-    return dict(text=text, data=data, lanes=G, dpl=DPL, lsh=lsh, n_families=len(families),
+    scans = [dict(head=c.head_id, sigma=c.sigma_id, first=c.ids[0], last=c.ids[-1], increments=c.m, slots=c.N)
+             for c in chains]
+    return dict(text=text, data=data, lanes=G, dpl=DPL, lsh=lsh, n_families=len(families), scan_chains=scans,
                 family_sizes=[f.n for f in families], n_scalar_units=len(scalar_units),
                 spread_sizes=[f.n for f in ufams], n_spread_sums=NW, n_batches=n_batches[0],
                 n_reduced=NS, n_boundary=len(boundary), gather_width=width, wg=wg)

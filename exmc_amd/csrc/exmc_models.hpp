@@ -1743,6 +1743,35 @@ static __host__ __device__ __noinline__ double exmc_gen_erf_call(double x) { ret
 #define EXMC_GEN_BATCH_LOG1P(n, b) exmc::lane_batch<EXMC_GEN_LANES, n>(b, l, [](double a_) { return EXMC_GENL_LOG1P(a_); })
 #define EXMC_GEN_BATCH_RCP(n, b) exmc::lane_batch<EXMC_GEN_LANES, n>(b, l, [](double a_) { return 1.0 / a_; })
 #define EXMC_GEN_FENCE() exmc::wave_lds_fence()
+// scan chains of the 64-lane layout (codegen_lanes.py): a random walk s_e = head + sigma z_1 + ... +
+// sigma z_e as ONE wave-wide prefix sum, its adjoint as a suffix sum (exmc_device.hpp wave_scan_fwd /
+// wave_scan_bwd: the association order include/exmc_scan.h restates). v: this lane's N slots,
+// element 64 k + l. FWD publishes s_e (e <= m) in the strip at wo + e. BWD takes the lane's sums
+// dlogp/ds_e, writes sg A_e (A_e = the suffix sum) to the cell ga + e that the owner lane of z_e adds,
+// and leaves sz = sum_e z_e A_e (per lane over its slots, then the butterfly) and a0 = A_0 in every
+// lane. Elements past m select, never multiply by 0 (z of a padding element is any position entry).
+#define EXMC_GEN_SCAN_FWD(N, v, m, zo, h, sg, wo)                              \
+  do {                                                                        \
+    exmc::wave_scan_fwd<N>(v);                                                \
+    _Pragma("unroll") for (int k_ = 0; k_ < (N); k_++)                        \
+      if (l + 64 * k_ <= (m)) EXMC_GEN_SH((wo) + l + 64 * k_) = (v)[k_];     \
+    exmc::wave_lds_fence();                                                   \
+  } while (0)
+#define EXMC_GEN_SCAN_BWD(N, v, m, zo, sg, we, ww, ga, sz, a0)                 \
+  do {                                                                        \
+    exmc::wave_scan_bwd<N>(v);                                                \
+    double p_[1] = {0.0};                                                     \
+    _Pragma("unroll") for (int k_ = 0; k_ < (N); k_++) {                      \
+      const int e_ = l + 64 * k_;                                             \
+      const bool in_ = e_ >= 1 && e_ <= (m);                                  \
+      const double z_ = EXMC_GEN_SH(EXMC_GEN_IT((zo) + e_));                  \
+      if (in_) EXMC_GEN_SH((ga) + e_) = (sg) * (v)[k_];                       \
+      p_[0] = in_ ? p_[0] + z_ * (v)[k_] : p_[0];                             \
+    }                                                                         \
+    exmc::group_allsum_n<64, 1, EXMC_GEN_XROW>(p_);                           \
+    (sz) = p_[0];                                                             \
+    (a0) = exmc::readlane_f64((v)[0], 0);                                     \
+  } while (0)
 // a pair of per-unit columns (codegen_lanes.py: interleaved over the units, 16-byte aligned in every placement of the
 // table): one global_load_dwordx4 / ds_read_b128 -- the alignment is what lets the compiler choose ds_read_b128 over
 // ds_read2_b64, a quarter of its LDS cycles
