@@ -24,7 +24,7 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_plugin_part.hip"),
     COMMON_SRC,
     os.path.join(HERE, "csrc", "exmc_plugin_kernels.inc"),
-    os.path.join(HERE, "csrc", "exmc_plugin_layouts.inc"),
+    os.path.join(HERE, "csrc", "exmc_layouts.inc"),
     os.path.join(ROOT, "include", "exmc_hip.h"),
     os.path.join(ROOT, "include", "exmc_detmath.h"),
     os.path.join(ROOT, "include", "exmc_logtab.h"),

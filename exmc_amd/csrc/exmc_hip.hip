@@ -15,6 +15,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -269,120 +270,57 @@ int upload_tuning(exmc_hip_model* m, const double* inv_mass) {
   return EXMC_OK;
 }
 
-// ---- model/lanes dispatch ---------------------------------------------------------------
-template <class M_, int G_, int LDSL_>
+// ---- model/lanes dispatch: the layouts of exmc_layouts.inc ------------------------------------
+enum { kRoleSample = 1, kRoleWarmup = 2, kRoleDense = 4, kRoleStream = 8 };
+
+template <class M_, int G_, int LDSL_, int kRoles = 0>
 struct Tag {
   using M = M_;
   static constexpr int G = G_;
   static constexpr int LDSL = LDSL_;  // tree-stack levels kept in LDS by nuts_kernel
+  static constexpr bool kStream = (kRoles & kRoleStream) != 0;   // stream-push and independent kernels
 };
 
 // LDS budget per one-wave workgroup: 4096 chains x G=16 lanes = 1024 workgroups = 4 per CU of
 // 160 KB; sv at 2048 chains x 64 lanes = 8 per CU.
-// kOneChain: the launches of the shared one-chain warmup (chain init, warmup kernels); a generated
-// lane layout of fewer than 64 lanes per chain has a form of its own for them (lanes = 64: the
-// chain's model terms over the whole wavefront, exmc_models.hpp CustomSplit)
+// kOneChain: the launches of the shared one-chain warmup (chain init, warmup kernels), which take
+// the EXMC_ONE_CHAIN rows too
 template <bool kOneChain = false, class F>
 int dispatch(exmc_hip_model* m, int lanes, F&& f) {
-  switch (m->kind) {
-#ifdef EXMC_CUSTOM_HEADER
-    case EXMC_MODEL_CUSTOM:   // a generated model (exmc_amd/codegen.py)
-#if defined(EXMC_GEN_LANES) && EXMC_GEN_LANES < 64
-      if constexpr (kOneChain) {
-        if (lanes == 64) return f(Tag<CustomSplit, EXMC_GEN_LANES, EXMC_GEN_LDSL>{}, m->cu);
-      }
-#endif
-#ifdef EXMC_GEN_ONE_LANE
-      if (lanes == 1) return f(Tag<Custom<1>, 1, EXMC_GEN_LDS_LEVELS>{}, m->cu);   // one lane per chain
-#endif
-#ifdef EXMC_GEN_VEC
-      if (lanes == 16) return f(Tag<Custom<16>, 16, 6>{}, m->cu);   // plates across lanes
-#endif
-#ifdef EXMC_GEN_LANES
-      if (lanes == EXMC_GEN_LANES)   // several dimensions per lane (codegen_lanes.py)
-        return f(Tag<Custom<EXMC_GEN_LANES>, EXMC_GEN_LANES, EXMC_GEN_LDSL>{}, m->cu);
-#endif
-      break;
-#endif
-#ifndef EXMC_ONLY_CUSTOM      // plug-in builds carry the generated model only
-// development builds for kernel work carry one model in one layout: -DEXMC_DEV_ES16_ONLY,
-// -DEXMC_DEV_ONLY=EXMC_DEV_SV64 (or _RADON64, _LOGISTIC16)
-#define EXMC_DEV_SV64 1
-#define EXMC_DEV_RADON64 2
-#define EXMC_DEV_LOGISTIC16 3
-#if defined(EXMC_DEV_ES16_ONLY)
-    case EXMC_MODEL_EIGHT_SCHOOLS:
-      if (lanes == 16) return f(Tag<EightSchools<16>, 16, 6>{}, m->es);
-      break;
-#elif defined(EXMC_DEV_ONLY)
-#if EXMC_DEV_ONLY == EXMC_DEV_SV64
-    case EXMC_MODEL_SV:
-      if (lanes == 64) return f(Tag<SV<64>, 64, 3>{}, m->sv);
-      break;
-#elif EXMC_DEV_ONLY == EXMC_DEV_RADON64
-    case EXMC_MODEL_RADON:
-      if (lanes == 64) return f(Tag<Radon<64>, 64, 3>{}, m->rd);
-      break;
-#elif EXMC_DEV_ONLY == EXMC_DEV_LOGISTIC16
-    case EXMC_MODEL_LOGISTIC:
-      if (lanes == 16) return f(Tag<Logistic<16>, 16, 2>{}, m->lg);
-      if (lanes == 64) return f(Tag<Logistic<64>, 64, 2>{}, m->lg);
-      break;
-#endif
-#else
-    case EXMC_MODEL_EIGHT_SCHOOLS:
-      switch (lanes) {
-        case 1: return f(Tag<EightSchools<1>, 1, 2>{}, m->es);
-        case 2: return f(Tag<EightSchools<2>, 2, 3>{}, m->es);
-        case 4: return f(Tag<EightSchools<4>, 4, 4>{}, m->es);
-        case 8: return f(Tag<EightSchools<8>, 8, 5>{}, m->es);
-        case 16: return f(Tag<EightSchools<16>, 16, 6>{}, m->es);
-        default: break;
-      }
-      break;
-    case EXMC_MODEL_SIMPLE:
-      if (lanes == 1) return f(Tag<Simple<1>, 1, 6>{}, m->sp);
-      break;
-    case EXMC_MODEL_SV:
-      switch (lanes) {
-        case 32: return f(Tag<SV<32>, 32, 2>{}, m->sv);
-        case 64: return f(Tag<SV<64>, 64, 3>{}, m->sv);
-        default: break;
-      }
-      break;
-    case EXMC_MODEL_SV_NCP:
-      if (lanes == 64) return f(Tag<SVNcp<64>, 64, 3>{}, m->sv);
-      break;
-    case EXMC_MODEL_LOGISTIC:
-      switch (lanes) {
-        case 4: return f(Tag<Logistic<4>, 4, 2>{}, m->lg);   // matrix-core path
-        case 8: return f(Tag<Logistic<8>, 8, 2>{}, m->lg);
-        case 16: return f(Tag<Logistic<16>, 16, 2>{}, m->lg);
-        case 64: return f(Tag<Logistic<64>, 64, 2>{}, m->lg);   // one chain per wave: the warmup's layout
-        default: break;
-      }
-      break;
-    case EXMC_MODEL_RADON:
-      switch (lanes) {
-        case 32: return f(Tag<Radon<32>, 32, 2>{}, m->rd);
-        case 64: return f(Tag<Radon<64>, 64, 3>{}, m->rd);
-        default: break;
-      }
-      break;
-#endif
-#endif
-    default: break;
-  }
+#define EXMC_ONE_CHAIN(K, L, M, G, LDSL, mem, roles) \
+  if constexpr (kOneChain) if (m->kind == K && lanes == L) return f(Tag<M, G, LDSL>{}, m->mem);
+#define EXMC_LAYOUT(K, L, M, LDSL, mem, roles, ...) \
+  if (m->kind == K && lanes == L) return f(Tag<M, L, LDSL, roles>{}, m->mem);
+#include "exmc_layouts.inc"
   return fail(EXMC_ERR_UNSUPPORTED, "model kind / lanes_per_chain combination not compiled in");
 }
 
-// the layouts that carry a dense mass matrix: a whole chain in one lane, or eight_schools' row
-// layout (16 lanes, one dimension per lane) through RowDenseModel
+// the layouts that carry a dense mass matrix: a whole chain in one lane, or a row with a dense model
 bool dense_layout_ok(const exmc_hip_model* m, int lanes) {
-  return lanes == 1 || (m->kind == EXMC_MODEL_EIGHT_SCHOOLS && lanes == 16) ||
-         (m->kind == EXMC_MODEL_SV && lanes == 64) || (m->kind == EXMC_MODEL_RADON && lanes == 64) ||
-         (m->kind == EXMC_MODEL_SV_NCP && lanes == 64) ||
-         (m->kind == EXMC_MODEL_LOGISTIC && lanes == 16);
+  bool ok = lanes == 1;
+#define EXMC_LAYOUT(K, L, M, LDSL, mem, roles, DL, ...) \
+  ok = ok || (m->kind == K && lanes == L && !std::is_void_v<__VA_ARGS__>);
+#include "exmc_layouts.inc"
+  return ok;
+}
+
+// the kind's lanes for a role: those of its first row with the role, else 1
+int role_lanes(int kind, int role) {
+#define EXMC_ONE_CHAIN(K, L, M, G, LDSL, mem, roles) \
+  if (kind == K && ((roles) & role)) return L;
+#define EXMC_LAYOUT(K, L, M, LDSL, mem, roles, ...) \
+  if (kind == K && ((roles) & role)) return L;
+#include "exmc_layouts.inc"
+  return 1;
+}
+
+// the sampling layout behind a one-chain form at `lanes`, else `lanes`
+int sampling_lanes(int kind, int lanes) {
+#define EXMC_ONE_CHAIN(K, L, M, G, LDSL, mem, roles) \
+  if (kind == K && lanes == L) return G;
+#define EXMC_LAYOUT(...)
+#include "exmc_layouts.inc"
+  return lanes;
 }
 
 // covp[s GD + i] = cov[rank(i)][s], cholp[j GD + i] = chol[j][rank(i)], zero columns past D
@@ -410,37 +348,16 @@ int ensure_densep(exmc_hip_model* m, int GD) {
 // dispatch for the launches whose mass-dependent operations depend on the dense mode
 template <bool kOneChain = false, class F>
 int dispatch_mass(exmc_hip_model* m, int lanes, bool dense, F&& f) {
-#if !defined(EXMC_ONLY_CUSTOM) && !defined(EXMC_DEV_ONLY)
-  if (dense && m->kind == EXMC_MODEL_EIGHT_SCHOOLS && lanes == 16)
-    return f(Tag<RowDenseModel<EightSchools<16>>, 16, 6>{}, m->es);
-  if (dense && m->kind == EXMC_MODEL_SV && lanes == 64)
-    return f(Tag<LaneDenseModel<SV<64>, 64>, 64, 2>{}, m->sv);
-  if (dense && m->kind == EXMC_MODEL_SV_NCP && lanes == 64)
-    return f(Tag<LaneDenseModel<SVNcp<64>, 64>, 64, 2>{}, m->sv);
-  if (dense && m->kind == EXMC_MODEL_RADON && lanes == 64)
-    return f(Tag<LaneDenseModel<Radon<64>, 64>, 64, 2>{}, m->rd);
-  if (dense && m->kind == EXMC_MODEL_LOGISTIC && lanes == 16)
-    return f(Tag<LaneDenseModel<Logistic<16>, 16>, 16, 2>{}, m->lg);
+#ifndef EXMC_DEV_ONLY   // kernel-work builds carry no dense variant
+#define EXMC_LAYOUT(K, L, M, LDSL, mem, roles, DL, ...)                                 \
+  if constexpr (!std::is_void_v<__VA_ARGS__>)                                          \
+    if (dense && m->kind == K && lanes == L) return f(Tag<__VA_ARGS__, L, DL>{}, m->mem);
+#include "exmc_layouts.inc"
 #endif
   return dispatch<kOneChain>(m, lanes, f);
 }
 
-int default_lanes(int kind) {
-  switch (kind) {
-    case EXMC_MODEL_EIGHT_SCHOOLS: return 16;
-    case EXMC_MODEL_SIMPLE: return 1;
-    case EXMC_MODEL_SV: return 64;
-    case EXMC_MODEL_SV_NCP: return 64;
-    case EXMC_MODEL_LOGISTIC: return 16;
-    case EXMC_MODEL_RADON: return 64;
-#if defined(EXMC_GEN_LANES)
-    case EXMC_MODEL_CUSTOM: return EXMC_GEN_LANES;
-#elif defined(EXMC_GEN_VEC)
-    case EXMC_MODEL_CUSTOM: return 16;
-#endif
-    default: return 1;
-  }
-}
+int default_lanes(int kind) { return role_lanes(kind, kRoleSample); }
 
 int resolve_lanes(const exmc_hip_model* m, int lanes) { return lanes > 0 ? lanes : default_lanes(m->kind); }
 
@@ -485,25 +402,6 @@ int set_flat_order(exmc_hip_model* m, const int32_t* perm) {
   return EXMC_OK;
 }
 
-// the kinds whose free-RV names the kind fixes: ids sorted as strings (point_map.ex:37)
-int default_flat_order(exmc_hip_model* m) {
-  std::vector<std::string> names;
-  if (m->kind == EXMC_MODEL_SV || m->kind == EXMC_MODEL_SV_NCP) {   // kernel order s_1..s_T (z_t), sigma, nu
-    for (int t = 1; t <= m->d - 2; t++) names.push_back("s_" + std::to_string(t));
-    names.push_back("sigma");
-    names.push_back("nu");
-  } else if (m->kind == EXMC_MODEL_LOGISTIC) {   // kernel order alpha, beta_1..beta_K
-    names.push_back("alpha");
-    for (int j = 1; j < m->d; j++) names.push_back("beta_" + std::to_string(j));
-  } else {
-    return EXMC_OK;   // sorted already (eight_schools, simple, generated models) or caller-defined (radon)
-  }
-  std::vector<int32_t> perm(m->d);
-  for (int i = 0; i < m->d; i++) perm[i] = i;
-  std::sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return names[a] < names[b]; });
-  return set_flat_order(m, perm.data());
-}
-
 const uint64_t* zig_ki(exmc_hip_model* m) { return m->zig.as<uint64_t>(); }
 const double* zig_wi(exmc_hip_model* m) { return m->zig.as<double>() + 256; }
 const double* zig_fi(exmc_hip_model* m) { return m->zig.as<double>() + 512; }
@@ -536,28 +434,6 @@ int launch_init(exmc_hip_model* m, int lanes, int C, int chain_lo, uint64_t seed
   };
   return one_chain ? dispatch<true>(m, lanes, launch) : dispatch(m, lanes, launch);
 }
-
-// the kernels a push-style stream may run: each kind in its default layout
-template <class M> inline constexpr bool kStreamKernel = false;
-#if !defined(EXMC_ONLY_CUSTOM) && !defined(EXMC_DEV_ONLY)
-template <> inline constexpr bool kStreamKernel<EightSchools<16>> = true;
-template <> inline constexpr bool kStreamKernel<Simple<1>> = true;
-template <> inline constexpr bool kStreamKernel<SV<64>> = true;
-template <> inline constexpr bool kStreamKernel<SVNcp<64>> = true;
-template <> inline constexpr bool kStreamKernel<Logistic<16>> = true;
-template <> inline constexpr bool kStreamKernel<Radon<64>> = true;
-#endif
-#ifdef EXMC_CUSTOM_HEADER
-#ifdef EXMC_GEN_ONE_LANE
-template <> inline constexpr bool kStreamKernel<Custom<1>> = true;
-#endif
-#ifdef EXMC_GEN_VEC
-template <> inline constexpr bool kStreamKernel<Custom<16>> = true;
-#endif
-#ifdef EXMC_GEN_LANES
-template <> inline constexpr bool kStreamKernel<Custom<EXMC_GEN_LANES>> = true;
-#endif
-#endif
 
 // dense: run under the dense mass installed on the handle (m->dense) instead of m->tuning's diagonal
 int launch_nuts(exmc_hip_model* m, bool dense, int lanes, int C, int n_draws, int draw_offset, double eps,
@@ -595,7 +471,7 @@ int launch_nuts(exmc_hip_model* m, bool dense, int lanes, int C, int n_draws, in
     }
     P.simds = m->simds;
     if (progress) {
-      if constexpr (kStreamKernel<M>) {
+      if constexpr (T::kStream) {
         if (timed) HIP_TRY(hipEventRecord(m->ev0, m->stream));
         const size_t lds_s = nuts_lds_bytes<M, T::LDSL, M::kNutsZigInLds>();
         EXMC_KLAUNCH(m->device, (nuts_kernel<M, T::G, T::LDSL, false, true>), grid, dim3(kNutsBlock), lds_s,
@@ -777,6 +653,13 @@ TraceDev trace_view(void* base, const TraceLayout& L) {
   return t;
 }
 
+TraceDev to_dev(const exmc_hip_trace& t) {
+  return TraceDev{t.draws, t.logp, t.tree_depth, t.n_steps, t.divergent, t.accept_prob, t.energy};
+}
+exmc_hip_trace to_abi(const TraceDev& t) {
+  return exmc_hip_trace{t.draws, t.logp, t.tree_depth, t.n_steps, t.divergent, t.accept_prob, t.energy};
+}
+
 // copy a device-layout staging trace to the caller's host trace ([chain][draw][dim])
 int download_trace(exmc_hip_model* m, const TraceLayout& L, int S, int C, exmc_hip_trace out) {
   std::vector<char> h(L.total);
@@ -791,6 +674,24 @@ int download_trace(exmc_hip_model* m, const TraceLayout& L, int S, int C, exmc_h
   if (out.n_steps) transpose_trace_scalar(t.n_steps, out.n_steps, S, C);
   if (out.divergent) transpose_trace_scalar(t.divergent, out.divergent, S, C);
   return EXMC_OK;
+}
+
+// n draws of the one chain in m->state (sample/3 after its warmup, the pull-style stream) into the
+// staging trace and on to the caller's; *div: the draws' divergences
+int sample_one_chain(exmc_hip_model* m, bool dense, int lanes, int n, double eps, int max_depth,
+                     exmc_hip_trace tr, int32_t* div) {
+  TraceLayout L = trace_layout(n, m->d, 1);
+  int rc = m->trace.ensure(L.total);
+  if (rc) return rc;
+  rc = reset_counters(m);
+  if (rc) return rc;
+  rc = launch_nuts(m, dense, lanes, 1, n, 0, eps, max_depth, trace_view(m->trace.p, L), true);
+  if (rc) return rc;
+  rc = finish_timing(m);
+  if (rc) return rc;
+  rc = read_counters(m, nullptr, div);
+  if (rc) return rc;
+  return download_trace(m, L, n, 1, tr);
 }
 
 // ---- host-side adaptation: step_size.ex:13-50, mass_matrix.ex:40-97, sampler.ex:764-785 ----
@@ -1054,8 +955,7 @@ int run_warmup_device(exmc_hip_model* m, int lanes, exmc_hip_opts o, exmc_hip_tu
     }
     size_t lds_bytes = nuts_lds_bytes<M, T::LDSL>();
     P.stage_model = 0;
-    if (M::kStageDoubles > 0 && lds_bytes + (size_t)M::kStageDoubles * 8 <= 160 * 1024 &&
-        (m->kind != EXMC_MODEL_LOGISTIC || m->lg.Npad <= 512)) {
+    if (M::kStageDoubles > 0 && lds_bytes + (size_t)M::kStageDoubles * 8 <= 160 * 1024 && M::stage_ok(mc)) {
       P.stage_model = 1;
       lds_bytes += (size_t)M::kStageDoubles * 8;
     }
@@ -1113,22 +1013,8 @@ int run_warmup_device(exmc_hip_model* m, int lanes, exmc_hip_opts o, exmc_hip_tu
   return EXMC_OK;
 }
 
-// sample_chains(..., vectorized: false): the kinds' default layouts carry the independent-adaptation
-// kernel (exmc_nuts.hpp indep_kernel), like the stream form
-template <class M> inline constexpr bool kIndepKernel = kStreamKernel<M>;
-#if defined(EXMC_DEV_ES16_ONLY)
-template <> inline constexpr bool kIndepKernel<EightSchools<16>> = true;
-#elif defined(EXMC_DEV_ONLY)
-#if EXMC_DEV_ONLY == EXMC_DEV_SV64
-template <> inline constexpr bool kIndepKernel<SV<64>> = true;
-#elif EXMC_DEV_ONLY == EXMC_DEV_RADON64
-template <> inline constexpr bool kIndepKernel<Radon<64>> = true;
-#elif EXMC_DEV_ONLY == EXMC_DEV_LOGISTIC16
-template <> inline constexpr bool kIndepKernel<Logistic<16>> = true;
-#endif
-#endif
-
-// one launch: every chain of [chain_lo, chain_hi) adapts and samples on its own (indep_kernel)
+// one launch: every chain of [chain_lo, chain_hi) adapts and samples on its own (indep_kernel); the
+// layouts with kRoleStream carry it (sample_chains(..., vectorized: false))
 int launch_independent(exmc_hip_model* m, int lanes, int C, exmc_hip_opts o, TraceDev tr, double* tune_dev) {
   if (o.max_tree_depth < 1 || o.max_tree_depth > kMaxLevels)
     return fail(EXMC_ERR_BADARG, "max_tree_depth out of range");
@@ -1159,7 +1045,7 @@ int launch_independent(exmc_hip_model* m, int lanes, int C, exmc_hip_opts o, Tra
   return dispatch(m, lanes, [&](auto tag, const auto& mc) {
     using T = decltype(tag);
     using M = typename T::M;
-    if constexpr (kIndepKernel<M>) {
+    if constexpr (T::kStream) {
       dim3 grid = grid_for(C, T::G, kNutsBlock);
       const size_t nthreads = (size_t)grid.x * kNutsBlock;
       constexpr int kSpill = (kMaxLevels > T::LDSL) ? (kMaxLevels - T::LDSL) : 1;
@@ -1194,6 +1080,212 @@ int check_model(const exmc_hip_model* m) {
   return EXMC_OK;
 }
 
+// ---- creating a handle: one function per kind ---------------------------------------------------
+// Each checks data / n_data, sets d and the constants, uploads the kind's device data image to
+// m->data, and names the free variables in kernel order where the kind fixes them (the flat order
+// sorts them as strings, point_map.ex:37). No names: the kernel order is sorted already
+// (eight_schools, simple, generated models) or the caller's to state (radon).
+using Names = std::vector<std::string>;
+
+double log2pi32() { return f32r(std::log(f32r(2.0 * M_PI))); }
+
+int upload_image(exmc_hip_model* m, const std::vector<double>& image) {
+  int rc = m->data.ensure(image.size() * 8);
+  if (rc) return rc;
+  if (hipMemcpy(m->data.p, image.data(), image.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(EXMC_ERR_HIP, "model data upload failed");
+  return EXMC_OK;
+}
+
+int create_eight_schools(exmc_hip_model* m, const double* data, int n_data, Names&) {
+  if (n_data != 16 || !data) return fail(EXMC_ERR_BADARG, "eight_schools needs y[8],sigma[8]");
+  m->d = 10;
+  for (int j = 0; j < 8; j++) {
+    m->es.y[j] = data[j];
+    m->es.sg[j] = data[8 + j];
+    m->es.lsg[j] = std::log(data[8 + j]);
+  }
+  m->es.c_mu = log2pi32() + 2.0 * std::log(5.0);
+  m->es.c_hc = f32r(std::log(2.0 / M_PI)) - std::log(5.0);
+  m->es.c1 = log2pi32() + 2.0 * 0.0;
+  return EXMC_OK;
+}
+
+int create_simple(exmc_hip_model* m, const double* data, int n_data, Names&) {
+  if (n_data < 1 || n_data > 64 || !data) return fail(EXMC_ERR_BADARG, "simple needs 1..64 observations");
+  m->d = 2;
+  m->sp.n = n_data;
+  for (int i = 0; i < n_data; i++) m->sp.y[i] = data[i];
+  m->sp.c_mu = log2pi32() + 2.0 * std::log(5.0);
+  m->sp.log2pi32 = log2pi32();
+  m->sp.tiny32 = f32r(1.0e-30);
+  return EXMC_OK;
+}
+
+// sv and sv_ncp: the same data and constants (SVNcp<64> reads SV's); kernel order s_1..s_T (z_t), sigma, nu
+int create_sv(exmc_hip_model* m, const double* data, int n_data, Names& names) {
+  if (n_data != 100 || !data) return fail(EXMC_ERR_BADARG, "sv is compiled for T = 100 returns");
+  m->d = 102;
+  static const double lanczos[9] = {0.99999999999980993,  676.5203681218851,     -1259.1392167224028,
+                                    771.32342877765313,   -176.61502916214059,   12.507343278686905,
+                                    -0.13857109526572012, 9.9843695780195716e-6, 1.5056327351493116e-7};
+  for (int i = 0; i < 100; i++) m->sv.r[i] = data[i];
+  for (int i = 0; i < 9; i++) m->sv.lanczos[i] = f32r(lanczos[i]);
+  m->sv.half_log_2pi32 = f32r(0.5 * std::log(2.0 * M_PI));
+  m->sv.log2pi32 = log2pi32();
+  m->sv.pi32 = f32r(M_PI);
+  m->sv.tiny32 = f32r(1.0e-30);
+  m->sv.lam_s = 50.0;
+  m->sv.lam_n = f32r(0.1);
+  m->sv.log_lam_s32 = f32r(std::log(50.0));
+  m->sv.log_lam_n32 = f32r(std::log(f32r(0.1)));
+  for (int t = 1; t <= 100; t++) names.push_back("s_" + std::to_string(t));
+  names.push_back("sigma");
+  names.push_back("nu");
+  return EXMC_OK;
+}
+
+// data = X[N][20] row-major, y[N]; the image: the data, then the MFMA operands Xa = [1 | X]
+// zero-padded to 24 / 32 features and Npad observations; kernel order alpha, beta_1..beta_20
+int create_logistic(exmc_hip_model* m, const double* data, int n_data, Names& names) {
+  if (!data || n_data < 21 || n_data % 21 != 0) return fail(EXMC_ERR_BADARG, "logistic needs X[N][20], y[N]");
+  const int N = n_data / 21, K = 20, Npad = (N + 15) / 16 * 16;
+  m->d = 21;
+  m->lg.N = N;
+  m->lg.Npad = Npad;
+  m->lg.c10 = log2pi32() + 2.0 * std::log(10.0);
+  m->lg.lo = f32r(1.0e-7);
+  m->lg.hi = 1.0 - f32r(1.0e-7);
+  std::vector<double> blob(data, data + n_data);
+  const size_t off_xat = blob.size(), off_xa32 = off_xat + (size_t)24 * Npad, off_yp = off_xa32 + (size_t)Npad * 32;
+  blob.resize(off_yp + Npad, 0.0);
+  for (int n = 0; n < N; n++) {
+    blob[off_xat + n] = 1.0;
+    blob[off_xa32 + (size_t)n * 32] = 1.0;
+    for (int j = 0; j < K; j++) {
+      const double x = data[(size_t)n * K + j];
+      blob[off_xat + (size_t)(1 + j) * Npad + n] = x;
+      blob[off_xa32 + (size_t)n * 32 + 1 + j] = x;
+    }
+    blob[off_yp + n] = data[(size_t)N * K + n];
+  }
+  int rc = upload_image(m, blob);
+  if (rc) return rc;
+  const double* base = m->data.as<double>();
+  m->lg.X = base;
+  m->lg.y = base + (size_t)N * K;
+  m->lg.XaT = base + off_xat;
+  m->lg.Xa32 = base + off_xa32;
+  m->lg.ypad = base + off_yp;
+  names.push_back("alpha");
+  for (int j = 1; j <= K; j++) names.push_back("beta_" + std::to_string(j));
+  return EXMC_OK;
+}
+
+// data = u[85], county_start[86], floor[N], y[N] (observations sorted by county); the image: the
+// data, then the 64-lane layout's copies of y, floor and county, zero-padded to 17 slots of 64 so
+// that lane l fetches slot s at base + 8 (64 s + l) with no clamp: [y | floor | 8 * county]
+// (RadonConsts::pobs; the county as the byte offset of its intercept in the kernel's alpha strip)
+int create_radon(exmc_hip_model* m, const double* data, int n_data, Names&) {
+  const int J = 85;
+  if (!data || n_data < 2 * J + 1 || (n_data - (2 * J + 1)) % 2 != 0) return fail(EXMC_ERR_BADARG, "radon needs u[85], start[86], floor[N], y[N]");
+  const int N = (n_data - (2 * J + 1)) / 2;
+  if ((int)data[J] != 0 || (int)data[2 * J] != N) return fail(EXMC_ERR_BADARG, "radon county offsets do not cover the observations");
+  // the 64-lane layout keeps a lane's observations in registers, 16 slots of 64 (exmc_models.hpp)
+  if (N > 1024) return fail(EXMC_ERR_UNSUPPORTED, "the radon kind holds at most 1024 observations");
+  for (int j = 0; j < J; j++)
+    if (data[J + j + 1] < data[J + j]) return fail(EXMC_ERR_BADARG, "radon county offsets must be non-decreasing");
+  m->d = J + 5;
+  m->rd.log2pi32 = log2pi32();
+  m->rd.tiny32 = f32r(1.0e-30);
+  m->rd.c_mu10 = log2pi32() + 2.0 * std::log(10.0);
+  m->rd.c_n5 = log2pi32() + 2.0 * std::log(5.0);
+  m->rd.c1 = log2pi32() + 2.0 * 0.0;
+  m->rd.c_hc = f32r(std::log(2.0 / M_PI)) - std::log(2.5);
+  constexpr int kRadonPad = Radon<64>::kObsPad;   // the capacity + one slot: every (slot, lane) index is an address
+  std::vector<double> blob(data, data + n_data);
+  const size_t off_pad = blob.size();
+  blob.resize(off_pad + (size_t)3 * kRadonPad, 0.0);
+  for (int i = 0; i < N; i++) {
+    blob[off_pad + i] = data[2 * J + 1 + N + i];
+    blob[off_pad + kRadonPad + i] = data[2 * J + 1 + i];
+  }
+  for (int j = 0; j < J; j++)
+    for (int i = (int)data[J + j]; i < (int)data[J + j + 1]; i++) {
+      const uint64_t off8 = 8ull * (uint64_t)j;
+      std::memcpy(&blob[off_pad + 2 * kRadonPad + i], &off8, 8);
+    }
+  int rc = upload_image(m, blob);
+  if (rc) return rc;
+  const double* base = m->data.as<double>();
+  m->rd.u = base;
+  m->rd.cs = base + J;
+  m->rd.fl = base + 2 * J + 1;
+  m->rd.y = base + 2 * J + 1 + N;
+  m->rd.pobs = base + off_pad;
+  return EXMC_OK;
+}
+
+#ifdef EXMC_CUSTOM_HEADER
+// a generated model: the image holds everything that depends on the data only, evaluated once (same
+// arithmetic as the kernels), then a lane layout's tables, folded when the model was generated
+int create_custom(exmc_hip_model* m, const double* data, int n_data, Names&) {
+  int kGenData = EXMC_GEN_NDATA;
+#ifdef EXMC_GEN_VEC
+  kGenData += EXMC_GEN_NVU + 16 * EXMC_GEN_NLR;
+#endif
+#ifdef EXMC_GEN_LANES
+  kGenData += EXMC_GEN_NLT;
+#endif
+  if (n_data != kGenData || (n_data > 0 && !data)) return fail(EXMC_ERR_BADARG, "generated model: data length differs from the one it was generated for");
+  m->d = EXMC_GEN_D;
+#ifdef EXMC_GEN_VEC
+  std::vector<double> folded(EXMC_GEN_NCONST + EXMC_GEN_NVC + 16 * EXMC_GEN_NLC);
+  {
+    const double* vdata = data + EXMC_GEN_NDATA;
+    double* vc = folded.data() + EXMC_GEN_NCONST;
+    exmc_gen_vfold(vdata, vc);
+    for (int l = 0; l < 16; l++)
+      exmc_gen_vfold_lane(vc, vdata + EXMC_GEN_NVU + l * EXMC_GEN_NLR,
+                          vc + EXMC_GEN_NVC + l * EXMC_GEN_NLC);
+  }
+#else
+  std::vector<double> folded(EXMC_GEN_NCONST);
+#endif
+#ifdef EXMC_GEN_ONE_LANE
+  exmc_gen_fold(data, folded.data());
+#endif
+#ifdef EXMC_GEN_LANES
+  while (folded.size() % 16) folded.push_back(0.0);   // the lane layout's table on a 128-byte boundary (codegen_lanes.py)
+#endif
+  const size_t n_folded = folded.size();
+#ifdef EXMC_GEN_LANES
+  folded.insert(folded.end(), data + EXMC_GEN_LOFF, data + EXMC_GEN_LOFF + EXMC_GEN_NLT);
+#endif
+  int rc = upload_image(m, folded);
+  if (rc) return rc;
+  m->cu.c = m->data.as<double>();
+  m->cu.vc = m->data.as<double>() + EXMC_GEN_NCONST;
+  m->cu.lt = m->data.as<double>() + n_folded;
+  return EXMC_OK;
+}
+#endif
+
+int create_kind(exmc_hip_model* m, const double* data, int n_data, Names& names) {
+  switch (m->kind) {
+    case EXMC_MODEL_EIGHT_SCHOOLS: return create_eight_schools(m, data, n_data, names);
+    case EXMC_MODEL_SIMPLE: return create_simple(m, data, n_data, names);
+    case EXMC_MODEL_SV:
+    case EXMC_MODEL_SV_NCP: return create_sv(m, data, n_data, names);
+    case EXMC_MODEL_LOGISTIC: return create_logistic(m, data, n_data, names);
+    case EXMC_MODEL_RADON: return create_radon(m, data, n_data, names);
+#ifdef EXMC_CUSTOM_HEADER
+    case EXMC_MODEL_CUSTOM: return create_custom(m, data, n_data, names);
+#endif
+    default: return fail(EXMC_ERR_UNSUPPORTED, "model kind not compiled into libexmc_hip");
+  }
+}
+
 }  // namespace
 
 // =========================================== C ABI ==========================================
@@ -1222,98 +1314,6 @@ int exmc_hip_model_create(int kind, int d, const double* data, int n_data, int d
   exmc_hip_model* m = new exmc_hip_model();
   m->kind = kind;
   m->device = device;
-  const double log2pi32 = f32r(std::log(f32r(2.0 * M_PI)));
-  switch (kind) {
-    case EXMC_MODEL_EIGHT_SCHOOLS: {
-      if (n_data != 16 || !data) { delete m; return fail(EXMC_ERR_BADARG, "eight_schools needs y[8],sigma[8]"); }
-      m->d = 10;
-      for (int j = 0; j < 8; j++) {
-        m->es.y[j] = data[j];
-        m->es.sg[j] = data[8 + j];
-        m->es.lsg[j] = std::log(data[8 + j]);
-      }
-      m->es.c_mu = log2pi32 + 2.0 * std::log(5.0);
-      m->es.c_hc = f32r(std::log(2.0 / M_PI)) - std::log(5.0);
-      m->es.c1 = log2pi32 + 2.0 * 0.0;
-      break;
-    }
-    case EXMC_MODEL_SIMPLE: {
-      if (n_data < 1 || n_data > 64 || !data) { delete m; return fail(EXMC_ERR_BADARG, "simple needs 1..64 observations"); }
-      m->d = 2;
-      m->sp.n = n_data;
-      for (int i = 0; i < n_data; i++) m->sp.y[i] = data[i];
-      m->sp.c_mu = log2pi32 + 2.0 * std::log(5.0);
-      m->sp.log2pi32 = log2pi32;
-      m->sp.tiny32 = f32r(1.0e-30);
-      break;
-    }
-    case EXMC_MODEL_SV:
-    case EXMC_MODEL_SV_NCP: {   // the same data and constants; SVNcp<64> reads SV's
-      if (n_data != 100 || !data) { delete m; return fail(EXMC_ERR_BADARG, "sv is compiled for T = 100 returns"); }
-      m->d = 102;
-      static const double lanczos[9] = {0.99999999999980993,  676.5203681218851,     -1259.1392167224028,
-                                        771.32342877765313,   -176.61502916214059,   12.507343278686905,
-                                        -0.13857109526572012, 9.9843695780195716e-6, 1.5056327351493116e-7};
-      for (int i = 0; i < 100; i++) m->sv.r[i] = data[i];
-      for (int i = 0; i < 9; i++) m->sv.lanczos[i] = f32r(lanczos[i]);
-      m->sv.half_log_2pi32 = f32r(0.5 * std::log(2.0 * M_PI));
-      m->sv.log2pi32 = log2pi32;
-      m->sv.pi32 = f32r(M_PI);
-      m->sv.tiny32 = f32r(1.0e-30);
-      m->sv.lam_s = 50.0;
-      m->sv.lam_n = f32r(0.1);
-      m->sv.log_lam_s32 = f32r(std::log(50.0));
-      m->sv.log_lam_n32 = f32r(std::log(f32r(0.1)));
-      break;
-    }
-    case EXMC_MODEL_LOGISTIC: {
-      // data = X[N][20] row-major, y[N]
-      if (!data || n_data < 21 || n_data % 21 != 0) { delete m; return fail(EXMC_ERR_BADARG, "logistic needs X[N][20], y[N]"); }
-      m->d = 21;
-      m->lg.N = n_data / 21;
-      m->lg.c10 = log2pi32 + 2.0 * std::log(10.0);
-      m->lg.lo = f32r(1.0e-7);
-      m->lg.hi = 1.0 - f32r(1.0e-7);
-      break;
-    }
-    case EXMC_MODEL_RADON: {
-      // data = u[85], county_start[86], floor[N], y[N] (observations sorted by county)
-      const int J = 85;
-      if (!data || n_data < 2 * J + 1 || (n_data - (2 * J + 1)) % 2 != 0) { delete m; return fail(EXMC_ERR_BADARG, "radon needs u[85], start[86], floor[N], y[N]"); }
-      const int N = (n_data - (2 * J + 1)) / 2;
-      if ((int)data[J] != 0 || (int)data[2 * J] != N) { delete m; return fail(EXMC_ERR_BADARG, "radon county offsets do not cover the observations"); }
-      // the 64-lane layout keeps a lane's observations in registers, 16 slots of 64 (exmc_models.hpp)
-      if (N > 1024) { delete m; return fail(EXMC_ERR_UNSUPPORTED, "the radon kind holds at most 1024 observations"); }
-      for (int j = 0; j < J; j++)
-        if (data[J + j + 1] < data[J + j]) { delete m; return fail(EXMC_ERR_BADARG, "radon county offsets must be non-decreasing"); }
-      m->d = J + 5;
-      m->rd.log2pi32 = log2pi32;
-      m->rd.tiny32 = f32r(1.0e-30);
-      m->rd.c_mu10 = log2pi32 + 2.0 * std::log(10.0);
-      m->rd.c_n5 = log2pi32 + 2.0 * std::log(5.0);
-      m->rd.c1 = log2pi32 + 2.0 * 0.0;
-      m->rd.c_hc = f32r(std::log(2.0 / M_PI)) - std::log(2.5);
-      break;
-    }
-#ifdef EXMC_CUSTOM_HEADER
-    case EXMC_MODEL_CUSTOM: {
-      int kGenData = EXMC_GEN_NDATA;
-#ifdef EXMC_GEN_VEC
-      kGenData += EXMC_GEN_NVU + 16 * EXMC_GEN_NLR;
-#endif
-#ifdef EXMC_GEN_LANES
-      kGenData += EXMC_GEN_NLT;
-#endif
-      if (n_data != kGenData || (n_data > 0 && !data)) { delete m; return fail(EXMC_ERR_BADARG, "generated model: data length differs from the one it was generated for"); }
-      m->d = EXMC_GEN_D;
-      break;
-    }
-#endif
-    default:
-      delete m;
-      return fail(EXMC_ERR_UNSUPPORTED, "model kind not compiled into libexmc_hip");
-  }
-  if (d != 0 && d != m->d) { delete m; return fail(EXMC_ERR_BADARG, "d does not match the model kind"); }
   auto bail = [&](int rc) { exmc_hip_model_destroy(m); return rc; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(EXMC_ERR_HIP, "hipSetDevice failed"));
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess)
@@ -1333,107 +1333,17 @@ int exmc_hip_model_create(int kind, int d, const double* data, int n_data, int d
       hipMemcpy(m->zig.as<double>() + 256, kZigWi, 256 * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(m->zig.as<double>() + 512, kZigFi, 256 * 8, hipMemcpyHostToDevice) != hipSuccess)
     return bail(fail(EXMC_ERR_HIP, "table upload failed"));
-  if (kind == EXMC_MODEL_LOGISTIC || kind == EXMC_MODEL_RADON) {
-    std::vector<double> blob(data, data + n_data);
-    size_t off_xat = 0, off_xa32 = 0, off_yp = 0;
-    if (kind == EXMC_MODEL_LOGISTIC) {
-      // MFMA operands: Xa = [1 | X] zero-padded to 24 / 32 features and Npad observations
-      const int N = m->lg.N, K = 20, Npad = (N + 15) / 16 * 16;
-      m->lg.Npad = Npad;
-      off_xat = blob.size();
-      blob.resize(blob.size() + (size_t)24 * Npad, 0.0);
-      off_xa32 = blob.size();
-      blob.resize(blob.size() + (size_t)Npad * 32, 0.0);
-      off_yp = blob.size();
-      blob.resize(blob.size() + (size_t)Npad, 0.0);
-      for (int n = 0; n < N; n++) {
-        blob[off_xat + n] = 1.0;
-        blob[off_xa32 + (size_t)n * 32] = 1.0;
-        for (int j = 0; j < K; j++) {
-          const double x = data[(size_t)n * K + j];
-          blob[off_xat + (size_t)(1 + j) * Npad + n] = x;
-          blob[off_xa32 + (size_t)n * 32 + 1 + j] = x;
-        }
-        blob[off_yp + n] = data[(size_t)N * K + n];
-      }
-    }
-    size_t off_pad = 0;
-    constexpr int kRadonPad = Radon<64>::kObsPad;   // the capacity + one slot: every (slot, lane) index is an address
-    if (kind == EXMC_MODEL_RADON) {
-      // the 64-lane layout's copies of y, floor and county, zero-padded to 17 slots of 64 so that lane l
-      // fetches slot s at base + 8 (64 s + l) with no clamp: [y | floor | 8 * county] (RadonConsts::pobs;
-      // the county as the byte offset of its intercept in the kernel's alpha strip, an integer)
-      const int J = 85, N = (n_data - (2 * J + 1)) / 2;
-      off_pad = blob.size();
-      blob.resize(blob.size() + (size_t)3 * kRadonPad, 0.0);
-      for (int i = 0; i < N; i++) {
-        blob[off_pad + i] = data[2 * J + 1 + N + i];
-        blob[off_pad + kRadonPad + i] = data[2 * J + 1 + i];
-      }
-      for (int j = 0; j < J; j++)
-        for (int i = (int)data[J + j]; i < (int)data[J + j + 1]; i++) {
-          const uint64_t off8 = 8ull * (uint64_t)j;
-          std::memcpy(&blob[off_pad + 2 * kRadonPad + i], &off8, 8);
-        }
-    }
-    rc = m->data.ensure(blob.size() * 8);
-    if (rc) return bail(rc);
-    if (hipMemcpy(m->data.p, blob.data(), blob.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(EXMC_ERR_HIP, "model data upload failed"));
-    const double* base = m->data.as<double>();
-    if (kind == EXMC_MODEL_LOGISTIC) {
-      m->lg.X = base;
-      m->lg.y = base + (size_t)m->lg.N * 20;
-      m->lg.XaT = base + off_xat;
-      m->lg.Xa32 = base + off_xa32;
-      m->lg.ypad = base + off_yp;
-    } else {
-      const int J = 85, N = (n_data - (2 * J + 1)) / 2;
-      m->rd.u = base;
-      m->rd.cs = base + J;
-      m->rd.fl = base + 2 * J + 1;
-      m->rd.y = base + 2 * J + 1 + N;
-      m->rd.pobs = base + off_pad;
-    }
-  }
-#ifdef EXMC_CUSTOM_HEADER
-  if (kind == EXMC_MODEL_CUSTOM) {
-    // everything that depends on the data only, evaluated once (same arithmetic as the kernels)
-#ifdef EXMC_GEN_VEC
-    std::vector<double> folded(EXMC_GEN_NCONST + EXMC_GEN_NVC + 16 * EXMC_GEN_NLC);
-    {
-      const double* vdata = data + EXMC_GEN_NDATA;
-      double* vc = folded.data() + EXMC_GEN_NCONST;
-      exmc_gen_vfold(vdata, vc);
-      for (int l = 0; l < 16; l++)
-        exmc_gen_vfold_lane(vc, vdata + EXMC_GEN_NVU + l * EXMC_GEN_NLR,
-                            vc + EXMC_GEN_NVC + l * EXMC_GEN_NLC);
-    }
-#else
-    std::vector<double> folded(EXMC_GEN_NCONST);
-#endif
-#ifdef EXMC_GEN_ONE_LANE
-    exmc_gen_fold(data, folded.data());
-#endif
-#ifdef EXMC_GEN_LANES
-    while (folded.size() % 16) folded.push_back(0.0);   // the lane layout's table on a 128-byte boundary (codegen_lanes.py)
-#endif
-    const size_t n_folded = folded.size();
-#ifdef EXMC_GEN_LANES
-    // the lane layout's tables were folded when the model was generated: they travel as they are
-    folded.insert(folded.end(), data + EXMC_GEN_LOFF, data + EXMC_GEN_LOFF + EXMC_GEN_NLT);
-#endif
-    rc = m->data.ensure(folded.size() * 8);
-    if (rc) return bail(rc);
-    if (hipMemcpy(m->data.p, folded.data(), folded.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(EXMC_ERR_HIP, "model data upload failed"));
-    m->cu.c = m->data.as<double>();
-    m->cu.vc = m->data.as<double>() + EXMC_GEN_NCONST;
-    m->cu.lt = m->data.as<double>() + n_folded;
-  }
-#endif
-  rc = default_flat_order(m);
+  Names names;
+  rc = create_kind(m, data, n_data, names);
   if (rc) return bail(rc);
+  if (d != 0 && d != m->d) return bail(fail(EXMC_ERR_BADARG, "d does not match the model kind"));
+  if (!names.empty()) {   // ids sorted as strings (point_map.ex:37)
+    std::vector<int32_t> perm(m->d);
+    for (int i = 0; i < m->d; i++) perm[i] = i;
+    std::sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return names[a] < names[b]; });
+    rc = set_flat_order(m, perm.data());
+    if (rc) return bail(rc);
+  }
   *out = m;
   return EXMC_OK;
 }
@@ -1463,27 +1373,8 @@ void exmc_hip_model_destroy(exmc_hip_model* m) {
 int exmc_hip_model_dim(const exmc_hip_model* m) { return m ? m->d : -1; }
 int exmc_hip_model_default_lanes(const exmc_hip_model* m) { return m ? default_lanes(m->kind) : -1; }
 
-int exmc_hip_model_default_warmup_lanes(const exmc_hip_model* m) {
-  if (!m) return -1;
-  // logistic: the shared warmup is ONE chain, so its 500 observations are best spread over a whole
-  // wavefront (8 per lane instead of 32: 158 -> 62 ms); sampling keeps 16 lanes per chain
-  if (m->kind == EXMC_MODEL_LOGISTIC) return 64;
-#if defined(EXMC_GEN_LANES) && EXMC_GEN_LANES < 64
-  // a generated lane layout: the chain's model terms over the whole wavefront (CustomSplit)
-  if (m->kind == EXMC_MODEL_CUSTOM) return 64;
-#endif
-  return default_lanes(m->kind);
-}
-int exmc_hip_model_default_dense_lanes(const exmc_hip_model* m) {
-  if (!m) return -1;
-  switch (m->kind) {
-    case EXMC_MODEL_SV: return 64;
-    case EXMC_MODEL_SV_NCP: return 64;
-    case EXMC_MODEL_RADON: return 64;
-    case EXMC_MODEL_LOGISTIC: return 16;
-    default: return 1;
-  }
-}
+int exmc_hip_model_default_warmup_lanes(const exmc_hip_model* m) { return m ? role_lanes(m->kind, kRoleWarmup) : -1; }
+int exmc_hip_model_default_dense_lanes(const exmc_hip_model* m) { return m ? role_lanes(m->kind, kRoleDense) : -1; }
 void* exmc_hip_model_stream(const exmc_hip_model* m) { return m ? (void*)m->stream : nullptr; }
 double exmc_hip_last_kernel_ms(const exmc_hip_model* m) { return m ? m->last_ms : 0.0; }
 
@@ -1672,11 +1563,9 @@ int warmup_impl(exmc_hip_model* m, const double* init_q, exmc_hip_opts o, const 
   if (rc) return rc;
   const char* hw = std::getenv("EXMC_HIP_HOST_WARMUP");
   const bool host_driven = hw && hw[0] == '1';
-#if defined(EXMC_GEN_LANES) && EXMC_GEN_LANES < 64
-  // the host-driven form launches the sampling kernels: a generated layout's one-chain form is not
-  // among them, so it runs in the sampling layout (other bits than the default, the same schedule)
-  if (host_driven && m->kind == EXMC_MODEL_CUSTOM && lanes == 64) lanes = EXMC_GEN_LANES;
-#endif
+  // the host-driven form launches the sampling kernels: a one-chain form is not among them, so it
+  // runs in its sampling layout (other bits than the default, the same schedule)
+  if (host_driven) lanes = sampling_lanes(m->kind, lanes);
   rc = launch_init(m, lanes, 1, 0, o.seed, init_q, !host_driven);
   if (rc) return rc;
   if (start && o.num_warmup == 0) {   // sampler.ex:195-196: nothing to tune
@@ -1780,11 +1669,8 @@ int exmc_hip_chains_advance(exmc_hip_model* m, int n_draws, int row_offset, exmc
   HIP_TRY(hipSetDevice(m->device));
   int rc = reset_counters(m);
   if (rc) return rc;
-  TraceDev t;
-  t.draws = tr.draws; t.logp = tr.logp; t.tree_depth = tr.tree_depth; t.n_steps = tr.n_steps;
-  t.divergent = tr.divergent; t.accept_prob = tr.accept_prob; t.energy = tr.energy;
-  rc = launch_nuts(m, m->dense_on, m->res_lanes, m->res_C, n_draws, row_offset, m->res_eps, m->res_max_depth, t,
-                   true);
+  rc = launch_nuts(m, m->dense_on, m->res_lanes, m->res_C, n_draws, row_offset, m->res_eps, m->res_max_depth,
+                   to_dev(tr), true);
   if (rc) return rc;
   rc = finish_timing(m);
   if (rc) return rc;
@@ -1817,12 +1703,8 @@ int exmc_hip_sample_chains_host(exmc_hip_model* m, const exmc_hip_tuning* tuning
   TraceLayout L = trace_layout(o.num_samples, m->d, C);
   int rc = m->trace.ensure(L.total);
   if (rc) return rc;
-  TraceDev t = trace_view(m->trace.p, L);
-  exmc_hip_trace dv;
-  dv.draws = t.draws; dv.logp = t.logp; dv.tree_depth = t.tree_depth; dv.n_steps = t.n_steps;
-  dv.divergent = t.divergent; dv.accept_prob = t.accept_prob; dv.energy = t.energy;
-  rc = exmc_hip_sample_chains(m, tuning, init_q, n_chains, chain_lo, chain_hi, o, dv,
-                              total_leapfrogs, total_divergences);
+  rc = exmc_hip_sample_chains(m, tuning, init_q, n_chains, chain_lo, chain_hi, o,
+                              to_abi(trace_view(m->trace.p, L)), total_leapfrogs, total_divergences);
   if (rc) return rc;
   return download_trace(m, L, o.num_samples, C, tr);
 }
@@ -1851,22 +1733,12 @@ int exmc_hip_sample_warm_host(exmc_hip_model* m, const double* init_q, exmc_hip_
   if (rc) return rc;
   rc = upload_tuning(m, tun.inv_mass);
   if (rc) return rc;
-  TraceLayout L = trace_layout(o.num_samples, m->d, 1);
-  rc = m->trace.ensure(L.total);
-  if (rc) return rc;
-  rc = reset_counters(m);
-  if (rc) return rc;
-  rc = launch_nuts(m, false, lanes, 1, o.num_samples, 0, tun.epsilon, o.max_tree_depth,
-                   trace_view(m->trace.p, L), true);
-  if (rc) return rc;
-  rc = finish_timing(m);
-  if (rc) return rc;
   int32_t div = 0;
-  rc = read_counters(m, nullptr, &div);
+  rc = sample_one_chain(m, false, lanes, o.num_samples, tun.epsilon, o.max_tree_depth, tr, &div);
   if (rc) return rc;
   if (divergences) *divergences = div + tun.warmup_divergences;  // stats.divergences, sampler.ex:245
   if (tuning_out) *tuning_out = tun;
-  return download_trace(m, L, o.num_samples, 1, tr);
+  return EXMC_OK;
 }
 
 int exmc_hip_sample_independent(exmc_hip_model* m, const double* init_q, int n_chains, int chain_lo,
@@ -1889,10 +1761,7 @@ int exmc_hip_sample_independent(exmc_hip_model* m, const double* init_q, int n_c
   if (rc) return rc;
   rc = reset_counters(m);
   if (rc) return rc;
-  TraceDev t;
-  t.draws = tr.draws; t.logp = tr.logp; t.tree_depth = tr.tree_depth; t.n_steps = tr.n_steps;
-  t.divergent = tr.divergent; t.accept_prob = tr.accept_prob; t.energy = tr.energy;
-  rc = launch_independent(m, lanes, C, o, t, m->io.as<double>());
+  rc = launch_independent(m, lanes, C, o, to_dev(tr), m->io.as<double>());
   if (rc) return rc;
   rc = finish_timing(m);
   if (rc) return rc;
@@ -1912,12 +1781,9 @@ int exmc_hip_sample_independent_host(exmc_hip_model* m, const double* init_q, in
   TraceLayout L = trace_layout(o.num_samples, m->d, C);
   int rc = m->trace.ensure(L.total);
   if (rc) return rc;
-  TraceDev t = trace_view(m->trace.p, L);
-  exmc_hip_trace dv;
-  dv.draws = t.draws; dv.logp = t.logp; dv.tree_depth = t.tree_depth; dv.n_steps = t.n_steps;
-  dv.divergent = t.divergent; dv.accept_prob = t.accept_prob; dv.energy = t.energy;
-  rc = exmc_hip_sample_independent(m, init_q, n_chains, chain_lo, chain_hi, o, dv, tuning_host,
-                                   total_leapfrogs, total_divergences);
+  rc = exmc_hip_sample_independent(m, init_q, n_chains, chain_lo, chain_hi, o,
+                                   to_abi(trace_view(m->trace.p, L)), tuning_host, total_leapfrogs,
+                                   total_divergences);
   if (rc) return rc;
   return download_trace(m, L, o.num_samples, C, tr);
 }
@@ -1936,21 +1802,12 @@ int exmc_hip_sample_dense_host(exmc_hip_model* m, const double* init_q, exmc_hip
   if (rc) return rc;
   rc = upload_tuning(m, tun.inv_mass);
   if (rc) return rc;
-  TraceLayout L = trace_layout(o.num_samples, m->d, 1);
-  rc = m->trace.ensure(L.total);
-  if (rc) return rc;
-  rc = reset_counters(m);
-  if (rc) return rc;
-  rc = launch_nuts(m, true, lanes, 1, o.num_samples, 0, tun.epsilon, o.max_tree_depth, trace_view(m->trace.p, L), true);
-  if (rc) return rc;
-  rc = finish_timing(m);
-  if (rc) return rc;
   int32_t div = 0;
-  rc = read_counters(m, nullptr, &div);
+  rc = sample_one_chain(m, true, lanes, o.num_samples, tun.epsilon, o.max_tree_depth, tr, &div);
   if (rc) return rc;
   if (divergences) *divergences = div + tun.warmup_divergences;
   if (tuning_out) *tuning_out = tun;
-  return download_trace(m, L, o.num_samples, 1, tr);
+  return EXMC_OK;
 }
 
 int exmc_hip_stream_begin(exmc_hip_model* m, const double* init_q, exmc_hip_opts o,
@@ -1980,21 +1837,11 @@ int exmc_hip_stream_next_host(exmc_hip_model* m, int n_draws, exmc_hip_trace tr,
   if (m->res_C != 1 || m->res_owner != kResStream) return fail(EXMC_ERR_BADARG, "no stream: call exmc_hip_stream_begin");
   if (n_draws < 1) return fail(EXMC_ERR_BADARG, "n_draws must be >= 1");
   HIP_TRY(hipSetDevice(m->device));
-  TraceLayout L = trace_layout(n_draws, m->d, 1);
-  int rc = m->trace.ensure(L.total);
-  if (rc) return rc;
-  rc = reset_counters(m);
-  if (rc) return rc;
-  rc = launch_nuts(m, false, m->res_lanes, 1, n_draws, 0, m->res_eps, m->res_max_depth,
-                   trace_view(m->trace.p, L), true);
-  if (rc) return rc;
-  rc = finish_timing(m);
-  if (rc) return rc;
   int32_t div = 0;
-  rc = read_counters(m, nullptr, &div);
+  int rc = sample_one_chain(m, false, m->res_lanes, n_draws, m->res_eps, m->res_max_depth, tr, &div);
   if (rc) return rc;
   if (divergences) *divergences = div;
-  return download_trace(m, L, n_draws, 1, tr);
+  return EXMC_OK;
 }
 
 namespace {
@@ -2023,14 +1870,7 @@ int stream_start_claimed(exmc_hip_model* m, int n_draws, exmc_hip_trace* view,
                    trace_view((char*)dev + 64, L), true, (int*)dev);
   if (rc) return rc;
   // with one chain the device layout [draw][dim][chain] is the host layout [draw][dim]
-  const TraceDev h = trace_view((char*)m->pin_host + 64, L);
-  view->draws = h.draws;
-  view->logp = h.logp;
-  view->tree_depth = h.tree_depth;
-  view->n_steps = h.n_steps;
-  view->divergent = h.divergent;
-  view->accept_prob = h.accept_prob;
-  view->energy = h.energy;
+  *view = to_abi(trace_view((char*)m->pin_host + 64, L));
   *progress = (const volatile int32_t*)m->pin_host;
   return EXMC_OK;
 }

@@ -19,12 +19,15 @@ __device__ __forceinline__ double clamp200(double z) { return fmax(-200.0, fmin(
 // kCoop: logp_grad is wave-cooperative (MFMA) and needs every lane of the wavefront active;
 // kExtraLdsDoubles: LDS scratch the functor wants per wavefront (Lane::sh points at it).
 // kStageDoubles: model data a single-workgroup kernel (the adaptation warmup) may copy into LDS
-// (Lane::xs); with one wavefront on the whole chip every global load is an exposed round trip.
+// (Lane::xs); with one wavefront on the whole chip every global load is an exposed round trip;
+// stage_ok(consts) (host): the data fit that image.
 struct ModelDefaults {
   static constexpr bool kVregMath = false;   // exp / log cores with VGPR-pinned coefficients
   static constexpr bool kCoop = false;
   static constexpr int kExtraLdsDoubles = 0;
   static constexpr int kStageDoubles = 0;
+  template <class C>
+  __host__ static bool stage_ok(const C&) { return true; }
   static constexpr int kStageRowOffset = 0;   // where Lane::xs points inside the image (doubles)
   // kLdsDataDoubles: observations every NUTS workgroup keeps in LDS for the whole kernel
   // (stage_data fills the image, Lane::xoff = its offset in the dynamic LDS array or -1)
@@ -760,6 +763,7 @@ struct Logistic : ModelDefaults {
   static constexpr int kRowDoubles = kObsCap * kRowStride;
   static constexpr int kStageRowOffset = 2 * EXMC_LOGTAB_ENTRIES;
   static constexpr int kStageDoubles = kStageRowOffset + kRowDoubles;
+  __host__ static bool stage_ok(const Consts& c) { return c.Npad <= kObsCap; }
   // G = 16: the sampling kernel as workgroups of eight wavefronts (two per SIMD, one workgroup per
   // compute unit) that share ONE image: 8192 chains x 16 lanes are exactly 256 such workgroups.
   // 88 KB of image + 6 KB of ziggurat tables leave one tree-stack level per wavefront in LDS
@@ -1166,6 +1170,7 @@ struct Logistic<4> : ModelDefaults {
   static constexpr int kStageStride = 514;
   static constexpr int kStageDoubles = 24 * kStageStride + 512;
   using Consts = LogisticConsts;
+  __host__ static bool stage_ok(const Consts& c) { return c.Npad <= 512; }
   struct Lane {
     double* sh;         // wavefront-shared LDS scratch: beta [24][16], grad [32][16], lik [16]
     const double* xs;   // LDS image of Xa / y, or null (operands then stream from L2)

@@ -1,4 +1,5 @@
-// The model-dependent kernel instantiations of a plug-in, once per layout the generated header carries.
+// The model-dependent kernel instantiations of a plug-in, once per layout the generated header carries
+// (the EXMC_MODEL_CUSTOM rows of exmc_layouts.inc: a plug-in build has no other).
 // Included by exmc_plugin_part.hip (EXMC_PLUGIN_PART = which part: explicit instantiation) and by
 // exmc_hip.hip under EXMC_PLUGIN_SPLIT (EXMC_PLUGIN_PART undefined: extern declarations of all).
 #ifdef EXMC_PLUGIN_PART
@@ -18,50 +19,42 @@
   EXMC_PK_DECL __global__ void init_chains_kernel<M, G>(InitParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void find_eps_kernel<M, G>(FindEpsParams, typename M::Consts);
 
+// and the chain init of a one-chain form (EXMC_ONE_CHAIN rows)
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 5
-#define EXMC_PK_LAYOUT(M, G, LDSL) EXMC_PK_AUX(M, G)
-#include "exmc_plugin_layouts.inc"
-#undef EXMC_PK_LAYOUT
+#define EXMC_LAYOUT(K, L, M, LDSL, ...) EXMC_PK_AUX(M, L)
+#define EXMC_ONE_CHAIN(K, L, M, G, LDSL, ...) \
+  EXMC_PK_DECL __global__ void init_chains_kernel<M, G>(InitParams, typename M::Consts);
+#include "exmc_layouts.inc"
 #endif
-// part 6 (and the chain init, with part 5): the one-chain form of a lane layout of fewer than
-// 64 lanes per chain (exmc_models.hpp CustomSplit) -- the kernels of the shared warmup only
-#if defined(EXMC_GEN_LANES) && (!defined(EXMC_PLUGIN_LAYOUT) || EXMC_PLUGIN_LAYOUT == 3)
-#if EXMC_GEN_LANES < 64
-#if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 5
-EXMC_PK_DECL __global__ void init_chains_kernel<CustomSplit, EXMC_GEN_LANES>(InitParams, typename CustomSplit::Consts);
-#endif
+// part 6: the warmup kernel of a one-chain form (a lane layout of fewer than 64 lanes per chain,
+// exmc_models.hpp CustomSplit) -- with the chain init, the kernels of the shared warmup only
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 6
-EXMC_PK_WARM(CustomSplit, EXMC_GEN_LANES, EXMC_GEN_LDSL, false)
-#endif
-#endif
+#define EXMC_LAYOUT(...)
+#define EXMC_ONE_CHAIN(K, L, M, G, LDSL, ...) EXMC_PK_WARM(M, G, LDSL, false)
+#include "exmc_layouts.inc"
 #endif
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 1
-#define EXMC_PK_LAYOUT(M, G, LDSL) EXMC_PK_NUTS(M, G, LDSL, false)
-#include "exmc_plugin_layouts.inc"
-#undef EXMC_PK_LAYOUT
+#define EXMC_LAYOUT(K, L, M, LDSL, ...) EXMC_PK_NUTS(M, L, LDSL, false)
+#include "exmc_layouts.inc"
 #endif
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 2
-#define EXMC_PK_LAYOUT(M, G, LDSL) EXMC_PK_NUTS(M, G, LDSL, true)
-#include "exmc_plugin_layouts.inc"
-#undef EXMC_PK_LAYOUT
+#define EXMC_LAYOUT(K, L, M, LDSL, ...) EXMC_PK_NUTS(M, L, LDSL, true)
+#include "exmc_layouts.inc"
 #endif
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 3
-#define EXMC_PK_LAYOUT(M, G, LDSL) EXMC_PK_WARM(M, G, LDSL, true)
-#include "exmc_plugin_layouts.inc"
-#undef EXMC_PK_LAYOUT
+#define EXMC_LAYOUT(K, L, M, LDSL, ...) EXMC_PK_WARM(M, L, LDSL, true)
+#include "exmc_layouts.inc"
 #endif
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 4
-#define EXMC_PK_LAYOUT(M, G, LDSL) EXMC_PK_WARM(M, G, LDSL, false)
-#include "exmc_plugin_layouts.inc"
-#undef EXMC_PK_LAYOUT
+#define EXMC_LAYOUT(K, L, M, LDSL, ...) EXMC_PK_WARM(M, L, LDSL, false)
+#include "exmc_layouts.inc"
 #endif
 // part 7: the independent-adaptation kernel (sample_chains vectorized: false), one per layout
 #define EXMC_PK_INDEP(M, G, LDSL) \
   EXMC_PK_DECL __global__ void indep_kernel<M, G, LDSL>(IndepParams, typename M::Consts);
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 7
-#define EXMC_PK_LAYOUT(M, G, LDSL) EXMC_PK_INDEP(M, G, LDSL)
-#include "exmc_plugin_layouts.inc"
-#undef EXMC_PK_LAYOUT
+#define EXMC_LAYOUT(K, L, M, LDSL, ...) EXMC_PK_INDEP(M, L, LDSL)
+#include "exmc_layouts.inc"
 #endif
 // part 8: the workgroup form of the sampling kernel for a lane layout that asks for it (EXMC_GEN_WG, codegen_lanes.py)
 #if defined(EXMC_GEN_LANES) && EXMC_GEN_WG && (!defined(EXMC_PLUGIN_LAYOUT) || EXMC_PLUGIN_LAYOUT == 3)
