@@ -11,7 +11,7 @@ defmodule Exmc.NUTS.HipSampler do
   NCP reconstruction and the stats maps are produced by the reference's own unchanged code.
   """
 
-  alias Exmc.NUTS.{HipExport, HipNative}
+  alias Exmc.NUTS.{HipCompareNative, HipExport, HipNative}
 
   @default_opts [num_warmup: 1000, num_samples: 1000, max_tree_depth: 10, target_accept: 0.8, seed: 0]
 
@@ -52,7 +52,8 @@ defmodule Exmc.NUTS.HipSampler do
   def compile_kind(kind, data_bin, pm, ncp_info, perm) do
     {:ok, ref} = HipNative.model_create(kind, data_bin)
     :ok = HipNative.model_set_flat_order(ref, perm)
-    %{ref: ref, pm: pm, ncp_info: ncp_info, perm: perm}
+    # kind and data ride along for model comparison (waic/3, loo/3: HipCompareNative.ic_stats/4)
+    %{ref: ref, pm: pm, ncp_info: ncp_info, perm: perm, model: {kind, data_bin}}
   end
 
   @doc """
@@ -172,6 +173,57 @@ defmodule Exmc.NUTS.HipSampler do
     init_q = init_q(compiled, Keyword.get(opts, :init_q))
     _tuning = HipNative.stream_begin(ref, init_q, opts[:num_warmup], opts[:max_tree_depth], opts[:target_accept], opts[:seed])
     HipNative.stream_run(ref, opts[:num_samples], receiver_pid)
+  end
+
+  # ---- model comparison (Exmc.ModelComparison, model_comparison.ex) ----
+
+  @doc """
+  `ModelComparison.waic/1` of a built kind over the datums of its data (one y_i, one return r_t;
+  DESIGN.md "Model comparison"): `draws` is the `[chain][draw][dim]` kernel-order binary the sampling
+  functions return (`trace.draws` of `sample_chains_vectorized/3`), opts `:num_chains` and
+  `:num_draws`. The per-datum statistics come from the device (`HipCompareNative.ic_stats/4`), the
+  totals from the reference's formulas -> `%{waic:, elpd_waic:, p_waic:, se:, n_obs:}`. A compiled
+  model of `compile_kind/5` only: a generated model has no per-datum terms
+  (`{:exmc_hip_error, 4, _}`).
+  """
+  def waic(%{model: model}, draws, opts) do
+    {lppd, p_waic, _elpd_loo, _p_loo} = ic_rows(model, draws, opts)
+    n = length(lppd)
+    lp = Enum.sum(lppd)
+    pw = Enum.sum(p_waic)
+    elpd_waic = lp - pw
+    elpd_pointwise = Enum.zip_with(lppd, p_waic, fn l, p -> l - p end)
+    se = if n > 1, do: :math.sqrt(n * variance(elpd_pointwise)), else: 0.0
+    %{waic: -2 * elpd_waic, elpd_waic: elpd_waic, p_waic: pw, se: se, n_obs: n}
+  end
+
+  @doc "`ModelComparison.loo/1` (plain importance-sampling LOO) the same way -> `%{loo:, elpd_loo:, p_loo:, se:, n_obs:}`"
+  def loo(%{model: model}, draws, opts) do
+    {_lppd, _p_waic, elpd_loo, p_loo} = ic_rows(model, draws, opts)
+    n = length(elpd_loo)
+    elpd = Enum.sum(elpd_loo)
+    se = if n > 1, do: :math.sqrt(n * variance(elpd_loo)), else: 0.0
+    %{loo: -2 * elpd, elpd_loo: elpd, p_loo: Enum.sum(p_loo), se: se, n_obs: n}
+  end
+
+  defp ic_rows(model, draws, opts) do
+    stats = HipCompareNative.ic_stats(model, draws, Keyword.fetch!(opts, :num_chains), Keyword.fetch!(opts, :num_draws))
+    vals = for <<x::float-64-native <- stats>>, do: x
+    n = div(length(vals), 4)
+    [a, b, c, d] = Enum.chunk_every(vals, n)
+    {a, b, c, d}
+  end
+
+  # model_comparison.ex:260-269
+  defp variance(values) do
+    n = length(values)
+
+    if n < 2 do
+      0.0
+    else
+      mean = Enum.sum(values) / n
+      Enum.sum(Enum.map(values, fn x -> (x - mean) * (x - mean) end)) / (n - 1)
+    end
   end
 
   # ---- layout helpers ----

@@ -29,6 +29,12 @@ EXPORTS = [
     "exmc_hip_leapfrog_chain_normal_host",
 ]
 
+# include/exmc_hip_compare.h: model comparison (WAIC / LOO) over a device trace
+COMPARE_EXPORTS = [
+    "exmc_hip_model_n_data", "exmc_hip_pointwise_loglik", "exmc_hip_ic_stats",
+    "exmc_hip_ic_stats_host", "exmc_hip_ic_stats_from_ll",
+]
+
 
 class ExmcHipError(RuntimeError):
     pass
@@ -135,6 +141,11 @@ def bind(path):
     L.exmc_hip_ess_bulk.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.exmc_hip_last_kernel_ms.argtypes = [vp]
     L.exmc_hip_last_kernel_ms.restype = C.c_double
+    L.exmc_hip_model_n_data.argtypes = [vp]
+    L.exmc_hip_pointwise_loglik.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.exmc_hip_ic_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.exmc_hip_ic_stats_host.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, dp]
+    L.exmc_hip_ic_stats_from_ll.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
     _libs[path] = L
     return L
 

@@ -4,6 +4,7 @@
 // log-density, gradient, tree merge and U-turn test runs in the HIP kernels. There is no CPU
 // fallback: without a HIP device every compute entry point returns EXMC_ERR_NO_DEVICE.
 #include "../../include/exmc_hip.h"
+#include "../../include/exmc_hip_compare.h"
 
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,7 @@
 #include "../../include/exmc_zig_tables.h"
 #include "exmc_kernels.hpp"
 #include "exmc_native_tree.hpp"
+#include "exmc_ic.hpp"
 
 using namespace exmc;
 
@@ -2430,6 +2432,226 @@ int exmc_hip_leapfrog_chain_normal_host(int device, int C, int d, const double* 
   if (!rc) rc = down(logp_chain, P.logp_chain, lps * 8);
   buf.release();
   return rc;
+}
+
+}  // extern "C"
+
+
+// ------------------------------------------------------------------------------------------
+// Model comparison (include/exmc_hip_compare.h; kernels in exmc_ic.hpp). The calls read the
+// handle's model data and nothing else, launch on its stream and allocate their scratch for the
+// call alone: the flat order, a dense mass and resident chains stay as they were.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// one device allocation that lives for one call
+struct CallBuf {
+  void* p = nullptr;
+  ~CallBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int alloc(size_t bytes) {
+    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
+    return EXMC_OK;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
+int ic_n_data(const exmc_hip_model* m) {
+  switch (m->kind) {
+    case EXMC_MODEL_SIMPLE: return m->sp.n;
+    case EXMC_MODEL_EIGHT_SCHOOLS: return 8;
+    case EXMC_MODEL_SV:
+    case EXMC_MODEL_SV_NCP: return 100;
+    case EXMC_MODEL_LOGISTIC: return m->lg.N;
+    case EXMC_MODEL_RADON: return (int)(m->rd.y - m->rd.fl);
+    default: return -1;
+  }
+}
+
+struct IcGrid {
+  long long chunk;
+  int n_chunks, block, yblocks;
+};
+IcGrid ic_grid(int S, int C, int N) {
+  IcGrid g;
+  const long long n = (long long)S * C;
+  g.chunk = ic_chunk(n);
+  g.n_chunks = (int)((n + g.chunk - 1) / g.chunk);
+  g.block = N >= kIcBlock ? kIcBlock : (N + 63) / 64 * 64;
+  g.yblocks = (N + g.block - 1) / g.block;
+  return g;
+}
+
+#ifndef EXMC_ONLY_CUSTOM
+// partials [n_chunks][kIcFields][N] -> stats [4][N]
+int ic_merge(hipStream_t stream, const double* part, const IcGrid& g, long long n, int N, double* stats) {
+  hipLaunchKernelGGL(ic_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, part, g.n_chunks,
+                     n, g.chunk, N, stats);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+
+template <class Src>
+int ic_launch(exmc_hip_model* m, const Src& src, bool matrix, const double* draws, int S, int C, int N,
+              double* out) {
+  const IcGrid g = ic_grid(S, C, N);
+  const size_t lds = ic_lds_bytes(m->d);
+  const dim3 grid((unsigned)g.n_chunks, (unsigned)g.yblocks);
+  if (matrix) {
+    if (lds > 64 * 1024) EXMC_KMAXLDS(pointwise_ll_kernel<Src>, lds);
+    HIP_TRY(hipEventRecord(m->ev0, m->stream));   // the timed region: the kernels alone
+    hipLaunchKernelGGL(pointwise_ll_kernel<Src>, grid, dim3(g.block), lds, m->stream, src, draws, S, m->d, C, N,
+                       g.chunk, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(m->ev1, m->stream));
+    return finish_timing(m);
+  }
+  CallBuf part;
+  int rc = part.alloc((size_t)g.n_chunks * kIcFields * N * 8);
+  if (rc) return rc;
+  if (lds > 64 * 1024) EXMC_KMAXLDS(ic_partials_kernel<Src>, lds);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  hipLaunchKernelGGL(ic_partials_kernel<Src>, grid, dim3(g.block), lds, m->stream, src, draws, S, m->d, C, N,
+                     g.chunk, part.as<double>());
+  HIP_TRY(hipGetLastError());
+  rc = ic_merge(m->stream, part.as<double>(), g, (long long)S * C, N, out);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the kernels: before `part` is freed
+}
+
+#endif
+
+// the kind's source of ll over a device trace; simple, eight_schools and sv keep their data in
+// the handle's constants, uploaded here for the call
+int ic_run(exmc_hip_model* m, bool matrix, const double* draws, int S, int d, int C, double* out) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  const int N = ic_n_data(m);
+  if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
+  if (!draws || !out || d != m->d || S < 1 || C < 1 || (long long)S * C < 2)
+    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+#ifdef EXMC_ONLY_CUSTOM
+  (void)matrix; (void)out;
+  return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
+#else
+  const double l2p = log2pi32();
+  std::vector<double> img;
+  if (m->kind == EXMC_MODEL_SIMPLE) img.assign(m->sp.y, m->sp.y + m->sp.n);
+  if (m->kind == EXMC_MODEL_EIGHT_SCHOOLS) {
+    img.assign(m->es.y, m->es.y + 8);
+    img.insert(img.end(), m->es.sg, m->es.sg + 8);
+  }
+  if (m->kind == EXMC_MODEL_SV || m->kind == EXMC_MODEL_SV_NCP) img.assign(m->sv.r, m->sv.r + 100);
+  CallBuf dimg;
+  if (!img.empty()) {
+    int rc = dimg.alloc(img.size() * 8);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(dimg.p, img.data(), img.size() * 8, hipMemcpyHostToDevice));
+  }
+  int rc = EXMC_OK;
+  switch (m->kind) {
+    case EXMC_MODEL_SIMPLE:
+      rc = ic_launch(m, IcSimpleSrc{dimg.as<double>(), l2p, m->sp.tiny32}, matrix, draws, S, C, N, out);
+      break;
+    case EXMC_MODEL_EIGHT_SCHOOLS:
+      rc = ic_launch(m, IcEightSchoolsSrc{dimg.as<double>(), l2p}, matrix, draws, S, C, N, out);
+      break;
+    case EXMC_MODEL_SV:
+    case EXMC_MODEL_SV_NCP: {
+      IcSvSrc src{};
+      src.r = dimg.as<double>();
+      for (int i = 0; i < 9; i++) src.lz[i] = m->sv.lanczos[i];
+      src.half_log_2pi32 = m->sv.half_log_2pi32;
+      src.pi32 = m->sv.pi32;
+      src.tiny32 = m->sv.tiny32;
+      src.ncp = m->kind == EXMC_MODEL_SV_NCP;
+      rc = ic_launch(m, src, matrix, draws, S, C, N, out);
+      break;
+    }
+    case EXMC_MODEL_LOGISTIC:
+      rc = ic_launch(m, IcLogisticSrc{m->lg.X, m->lg.y, m->lg.lo, m->lg.hi}, matrix, draws, S, C, N, out);
+      break;
+    case EXMC_MODEL_RADON:
+      rc = ic_launch(m, IcRadonSrc{m->rd.u, m->rd.cs, m->rd.fl, m->rd.y, m->rd.log2pi32, m->rd.tiny32}, matrix,
+                     draws, S, C, N, out);
+      break;
+  }
+  return rc;
+#endif
+}
+
+}  // namespace
+
+extern "C" {
+
+int exmc_hip_model_n_data(const exmc_hip_model* m) {
+  if (!m) return -1;
+  return ic_n_data(m);
+}
+
+int exmc_hip_pointwise_loglik(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
+                              double* ll_dev) {
+  return ic_run(m, true, draws_dev, n_draws, d, n_chains, ll_dev);
+}
+
+int exmc_hip_ic_stats(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
+                      double* stats_dev) {
+  return ic_run(m, false, draws_dev, n_draws, d, n_chains, stats_dev);
+}
+
+int exmc_hip_ic_stats_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains,
+                           double* stats_host) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  const int N = ic_n_data(m);
+  if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
+  if (!draws_host || !stats_host || d != m->d || n_draws < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
+    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  // [C][S][d] -> the device layout [S][d][C]
+  const int S = n_draws, C = n_chains;
+  std::vector<double> h((size_t)S * d * C);
+  for (int c = 0; c < C; c++)
+    for (int s = 0; s < S; s++)
+      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
+  CallBuf buf;
+  int rc = buf.alloc((h.size() + (size_t)4 * N) * 8);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  double* stats = buf.as<double>() + h.size();
+  rc = ic_run(m, false, buf.as<double>(), S, d, C, stats);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(stats_host, stats, (size_t)4 * N * 8, hipMemcpyDeviceToHost));
+  return EXMC_OK;
+}
+
+int exmc_hip_ic_stats_from_ll(int device, const double* ll_dev, int n_draws, int n_data, int n_chains,
+                              double* stats_dev) {
+  if (!ll_dev || !stats_dev || n_draws < 1 || n_data < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
+    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  int rc = select_device(device);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  // a generated model's plug-in carries no model-comparison kernels: libexmc_hip.so serves this call
+  return fail(EXMC_ERR_UNSUPPORTED, "model comparison: use libexmc_hip.so for the model-free reduction");
+#else
+  const int S = n_draws, C = n_chains, N = n_data;
+  const IcGrid g = ic_grid(S, C, N);
+  CallBuf part;
+  rc = part.alloc((size_t)g.n_chunks * kIcFields * N * 8);
+  if (rc) return rc;
+  const size_t lds = ic_lds_bytes(0);
+  hipLaunchKernelGGL(ic_partials_kernel<IcMatrixSrc>, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks), dim3(g.block),
+                     lds, (hipStream_t)0, IcMatrixSrc{ll_dev}, (const double*)nullptr, S, 0, C, N, g.chunk,
+                     part.as<double>());
+  HIP_TRY(hipGetLastError());
+  rc = ic_merge((hipStream_t)0, part.as<double>(), g, (long long)S * C, N, stats_dev);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)0));
+  return EXMC_OK;
+#endif
 }
 
 }  // extern "C"

@@ -231,7 +231,11 @@ def radon(data=None, sort_counties=True, builtin=False):
                                   waves_per_simd=1)
     blob = np.concatenate([np.asarray(u, float), np.asarray(start, float), np.asarray(floor, float),
                            np.asarray(y, float)])
-    return ModelSpec(RADON, "radon", blob, names, {"sigma_alpha": "log", "sigma_y": "log"}, init)
+    spec = ModelSpec(RADON, "radon", blob, names, {"sigma_alpha": "log", "sigma_y": "log"}, init)
+    # the handle's observation k (county-sorted) is the caller's observation datum_order[k]
+    # (exmc_amd/model_comparison.py maps per-datum results back through it)
+    spec.datum_order = obs
+    return spec
 
 
 def sv(returns):
