@@ -1291,6 +1291,45 @@ _FN1 = {"exp": "EXMC_GEN_EXP", "log": "EXMC_GEN_LOG", "log1p": "EXMC_GEN_LOG1P",
 _FN2 = {"max": "fmax", "min": "fmin"}
 
 
+def _reachable(roots, children):
+    """The nodes reachable from `roots`, in the order a depth-first walk first meets them.
+    children(i): the nodes i leads to -- none at a leaf, or where the walk is to stop."""
+    seen, order, stack = set(), [], list(roots)
+    while stack:
+        i = stack.pop()
+        if i in seen:
+            continue
+        seen.add(i)
+        order.append(i)
+        stack.extend(children(i))
+    return order
+
+
+def _lit_text(hexv, finite_only=True):
+    """A literal as C text. finite_only: an infinity or a NaN is an error (the plate layout of
+    codegen_vec.py alone has never checked, and prints what repr gives)."""
+    s = repr(float.fromhex(hexv))
+    if finite_only and ("inf" in s or "nan" in s):
+        raise CodegenError("non-finite literal")
+    return "(%s)" % s if s.startswith("-") else s
+
+
+def _expr_text(op, a, fn1=_FN1):
+    """Operator `op` applied to the argument texts `a`. fn1: the names of the one-argument
+    functions (each layout has a macro prefix of its own for the transcendentals)."""
+    if op in _BIN:
+        return "%s %s %s" % (a[0], _BIN[op], a[1])
+    if op == "neg":
+        return "-%s" % a[0]
+    if op in fn1:
+        return "%s(%s)" % (fn1[op], a[0])
+    if op in _FN2:
+        return "%s(%s, %s)" % (_FN2[op], a[0], a[1])
+    if op == "sel_gt":
+        return "(%s > %s) ? %s : %s" % tuple(a)
+    raise CodegenError("cannot emit %s" % op)
+
+
 def _lds_levels(d):
     per_level = (5 * d + 3) * 64 * 8
     return max(1, min(6, (56 * 1024) // per_level))
@@ -1309,16 +1348,7 @@ def _emit_no_one_lane(d):
 def _emit(g, total, grads, d):
     outputs = [total] + [x for x in grads if x is not None]
     # liveness: everything reachable from the outputs
-    live = set()
-    stack = list(outputs)
-    while stack:
-        i = stack.pop()
-        if i in live:
-            continue
-        live.add(i)
-        op = g.ops[i]
-        if op[0] not in ("lit", "data", "q"):
-            stack.extend(op[1:])
+    live = set(_reachable(outputs, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data", "q") else ()))
     # folded constants: const non-literal nodes read by a dynamic node (or being an output)
     slot = {}
     for a in outputs:
@@ -1331,24 +1361,12 @@ def _emit(g, total, grads, d):
             if g.const[a] and g.ops[a][0] != "lit" and a not in slot:
                 slot[a] = len(slot)
     # host-side nodes needed for the slots
-    host = set()
-    stack = list(slot)
-    while stack:
-        i = stack.pop()
-        if i in host:
-            continue
-        host.add(i)
-        op = g.ops[i]
-        if op[0] not in ("lit", "data"):
-            stack.extend(op[1:])
+    host = set(_reachable(slot, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data") else ()))
 
     def ref(i, dyn):
         op = g.ops[i]
         if op[0] == "lit":
-            s = repr(float.fromhex(op[1]))
-            if "inf" in s or "nan" in s:
-                raise CodegenError("non-finite literal")
-            return "(%s)" % s if s.startswith("-") else s
+            return _lit_text(op[1])
         if dyn and i in slot:
             return "c[%d]" % slot[i]
         if op[0] == "data":
@@ -1360,19 +1378,7 @@ def _emit(g, total, grads, d):
     def stmt(i, dyn):
         op = g.ops[i]
         a = [ref(x, dyn) for x in op[1:]] if op[0] not in ("lit", "data", "q") else []
-        if op[0] in _BIN:
-            e = "%s %s %s" % (a[0], _BIN[op[0]], a[1])
-        elif op[0] == "neg":
-            e = "-%s" % a[0]
-        elif op[0] in _FN1:
-            e = "%s(%s)" % (_FN1[op[0]], a[0])
-        elif op[0] in _FN2:
-            e = "%s(%s, %s)" % (_FN2[op[0]], a[0], a[1])
-        elif op[0] == "sel_gt":
-            e = "(%s > %s) ? %s : %s" % tuple(a)
-        else:
-            raise CodegenError("cannot emit %s" % op[0])
-        return "  const double t%d = %s;" % (i, e)
+        return "  const double t%d = %s;" % (i, _expr_text(op[0], a))
 
     L = []
     L.append("/* generated by exmc_amd/codegen.py -- do not edit. Included twice over: by")

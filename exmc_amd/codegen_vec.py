@@ -27,6 +27,9 @@ import numpy as np
 from . import codegen as cg
 
 G = 16
+# the lane function holds a handful of transcendentals: they are inlined (EXMC_GENV_*),
+# unlike the one-lane body's tens of calls (EXMC_GEN_*, exmc_models.hpp)
+_FN1V = {k: v.replace("EXMC_GEN_", "EXMC_GENV_") for k, v in cg._FN1.items()}
 
 
 class _VGraph(cg._Graph):
@@ -322,14 +325,8 @@ def generate(ir, ncp=True):
 
 def _emit(g, D, s_out, gown, sg, scal_lp, nlr):
     outputs = [x for x in s_out + [gown, scal_lp] + sg if x is not None]
-    live, stack = set(), list(outputs)
-    while stack:
-        i = stack.pop()
-        if i in live:
-            continue
-        live.add(i)
-        if g.ops[i][0] not in ("lit", "data", "q", "qown", "ldata"):
-            stack.extend(g.ops[i][1:])
+    live = set(cg._reachable(outputs, lambda i: g.ops[i][1:] if g.ops[i][0] not in
+                             ("lit", "data", "q", "qown", "ldata") else ()))
     uslot, lslot = {}, {}     # uniform / lane constants read by dynamic code (or being outputs)
 
     def want(a):
@@ -345,32 +342,20 @@ def _emit(g, D, s_out, gown, sg, scal_lp, nlr):
         for a in g.ops[i][1:]:
             want(a)
     # lane constants may read uniform constants: those need uniform slots too
-    lhost, stack = set(), list(lslot)
-    while stack:
-        i = stack.pop()
-        if i in lhost:
-            continue
-        lhost.add(i)
+    # (in the order of the walk, which numbers the slots)
+    lhost = cg._reachable(lslot, lambda i: [a for a in g.ops[i][1:] if g.lane[a]]
+                          if g.ops[i][0] not in ("lit", "data", "ldata") else ())
+    for i in lhost:
         if g.ops[i][0] not in ("lit", "data", "ldata"):
             for a in g.ops[i][1:]:
-                if g.lane[a]:
-                    stack.append(a)
-                elif g.ops[a][0] != "lit":
+                if not g.lane[a] and g.ops[a][0] != "lit":
                     want(a)
-    uhost, stack = set(), list(uslot)
-    while stack:
-        i = stack.pop()
-        if i in uhost:
-            continue
-        uhost.add(i)
-        if g.ops[i][0] not in ("lit", "data"):
-            stack.extend(g.ops[i][1:])
+    uhost = cg._reachable(uslot, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data") else ())
 
     def ref(i, where):
         op = g.ops[i]
         if op[0] == "lit":
-            s = repr(float.fromhex(op[1]))
-            return "(%s)" % s if s.startswith("-") else s
+            return cg._lit_text(op[1], finite_only=False)
         if where == "dyn":
             if i in uslot:
                 return "vc[%d]" % uslot[i]
@@ -390,22 +375,7 @@ def _emit(g, D, s_out, gown, sg, scal_lp, nlr):
 
     def stmt(i, where):
         op = g.ops[i]
-        a = [ref(x, where) for x in op[1:]]
-        if op[0] in cg._BIN:
-            e = "%s %s %s" % (a[0], cg._BIN[op[0]], a[1])
-        elif op[0] == "neg":
-            e = "-%s" % a[0]
-        elif op[0] in cg._FN1:
-            # the lane function holds a handful of transcendentals: they are inlined (EXMC_GENV_*),
-            # unlike the one-lane body's tens of calls (EXMC_GEN_*, exmc_models.hpp)
-            e = "%s(%s)" % (cg._FN1[op[0]].replace("EXMC_GEN_", "EXMC_GENV_"), a[0])
-        elif op[0] in cg._FN2:
-            e = "%s(%s, %s)" % (cg._FN2[op[0]], a[0], a[1])
-        elif op[0] == "sel_gt":
-            e = "(%s > %s) ? %s : %s" % tuple(a)
-        else:
-            raise cg.CodegenError("cannot emit %s" % op[0])
-        return "  const double t%d = %s;" % (i, e)
+        return "  const double t%d = %s;" % (i, cg._expr_text(op[0], [ref(x, where) for x in op[1:]], _FN1V))
 
     L = ["/* 16-lane layout (exmc_amd/codegen_vec.py): vdata = uniform constants, then 16 rows of"
          " EXMC_GEN_NLR\n * per-lane constants; vc / lc = what the host folds from them. */"]
