@@ -52,7 +52,7 @@ defmodule Exmc.NUTS.HipSampler do
   def compile_kind(kind, data_bin, pm, ncp_info, perm) do
     {:ok, ref} = HipNative.model_create(kind, data_bin)
     :ok = HipNative.model_set_flat_order(ref, perm)
-    # kind and data ride along for model comparison (waic/3, loo/3: HipCompareNative.ic_stats/4)
+    # kind and data ride along for model comparison (waic/3, loo/3: HipCompareNative.ic_stats/4; psis_loo/3: HipPsisNative.psis_stats/4)
     %{ref: ref, pm: pm, ncp_info: ncp_info, perm: perm, model: {kind, data_bin}}
   end
 
@@ -204,6 +204,44 @@ defmodule Exmc.NUTS.HipSampler do
     elpd = Enum.sum(elpd_loo)
     se = if n > 1, do: :math.sqrt(n * variance(elpd_loo)), else: 0.0
     %{loo: -2 * elpd, elpd_loo: elpd, p_loo: Enum.sum(p_loo), se: se, n_obs: n}
+  end
+
+  @doc """
+  Pareto-smoothed importance-sampling LOO (DESIGN.md "PSIS-LOO") the same way ->
+  `%{loo:, elpd_loo:, p_loo:, se:, n_obs:, pareto_k:, k_threshold:, n_high_k:}`: `pareto_k` is the list of
+  the datums' Pareto k (`:infinity` where the tail was too short to fit, `:nan` for a datum with a non-finite term), `k_threshold`
+  min(1 - 1/log10(n), 0.7) for n = num_chains * num_draws, `n_high_k` the number of datums not at or below it (`:infinity` and `:nan` count).
+  """
+  def psis_loo(%{model: model}, draws, opts) do
+    num_chains = Keyword.fetch!(opts, :num_chains)
+    num_draws = Keyword.fetch!(opts, :num_draws)
+    out = Exmc.NUTS.HipPsisNative.psis_stats(model, draws, num_chains, num_draws)
+    # +inf and NaN are not Erlang floats: decode them as atoms
+    vals =
+      for <<bits::64-native <- out>> do
+        case <<bits::64-native>> do
+          <<x::float-64-native>> -> x
+          _ -> if Bitwise.band(bits, 0x000FFFFFFFFFFFFF) == 0, do: :infinity, else: :nan
+        end
+      end
+
+    n = div(length(vals), 3)
+    [elpd_loo, p_loo, k] = Enum.chunk_every(vals, n)
+    thr = min(1.0 - 1.0 / :math.log10(num_chains * num_draws), 0.7)
+    finite = Enum.all?(elpd_loo ++ p_loo, &is_float/1)
+    elpd = if finite, do: Enum.sum(elpd_loo), else: :nan
+    se = if finite and n > 1, do: :math.sqrt(n * variance(elpd_loo)), else: if(finite, do: 0.0, else: :nan)
+
+    %{
+      loo: if(finite, do: -2 * elpd, else: :nan),
+      elpd_loo: elpd,
+      p_loo: if(finite, do: Enum.sum(p_loo), else: :nan),
+      se: se,
+      n_obs: n,
+      pareto_k: k,
+      k_threshold: thr,
+      n_high_k: Enum.count(k, fn v -> not (is_float(v) and v <= thr) end)
+    }
   end
 
   defp ic_rows(model, draws, opts) do

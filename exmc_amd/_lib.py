@@ -35,6 +35,9 @@ COMPARE_EXPORTS = [
     "exmc_hip_ic_stats_host", "exmc_hip_ic_stats_from_ll",
 ]
 
+# include/exmc_hip_psis.h (the end of exmc_hip_compare.h): PSIS-LOO with the Pareto k diagnostic
+PSIS_EXPORTS = ["exmc_hip_psis_stats", "exmc_hip_psis_stats_host", "exmc_hip_psis_stats_from_ll"]
+
 
 class ExmcHipError(RuntimeError):
     pass
@@ -146,6 +149,9 @@ def bind(path):
     L.exmc_hip_ic_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.exmc_hip_ic_stats_host.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, dp]
     L.exmc_hip_ic_stats_from_ll.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.exmc_hip_psis_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
+    L.exmc_hip_psis_stats_host.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_size_t, dp]
+    L.exmc_hip_psis_stats_from_ll.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
     _libs[path] = L
     return L
 

@@ -24,6 +24,7 @@
 #include "exmc_kernels.hpp"
 #include "exmc_native_tree.hpp"
 #include "exmc_ic.hpp"
+#include "exmc_psis.hpp"
 
 using namespace exmc;
 
@@ -2470,6 +2471,8 @@ int ic_n_data(const exmc_hip_model* m) {
   }
 }
 
+enum IcMode { kIcStats, kIcMatrix, kIcPsis };   // [4][N] statistics, the matrix, PSIS-LOO's [3][N]
+
 struct IcGrid {
   long long chunk;
   int n_chunks, block, yblocks;
@@ -2491,6 +2494,86 @@ int ic_merge(hipStream_t stream, const double* part, const IcGrid& g, long long 
                      n, g.chunk, N, stats);
   HIP_TRY(hipGetLastError());
   return EXMC_OK;
+}
+
+// ---- PSIS-LOO (exmc_psis.hpp) ----
+// the scratch of one call: the tables [Nb][P] of the sorted tails and their smoothed values, the
+// per-datum results of the tail kernel and the chunk states, for blocks of at most Nb datums
+struct PsisScratch {
+  CallBuf keys, idx, xs, meta, part;
+  int M = 0, P = 0;
+  IcGrid g{};
+  int alloc(int S, int C, int Nb) {
+    const long long n = (long long)S * C;
+    M = psis_tail_len(n);
+    P = psis_pow2(M);
+    g = ic_grid(S, C, Nb);
+    int rc = keys.alloc((size_t)Nb * P * 8);
+    if (!rc) rc = idx.alloc((size_t)Nb * P * 4);
+    if (!rc) rc = xs.alloc((size_t)Nb * P * 8);
+    if (!rc) rc = meta.alloc((size_t)Nb * kPsisMeta * 8);
+    if (!rc) rc = part.alloc((size_t)g.n_chunks * kPsisFields * Nb * 8);
+    if (rc) return rc;
+    // the tail kernel's dynamic LDS sits beside some 20 KB of static LDS: above 64 KB in all it has to
+    // be asked for, once per call and outside the timed region
+    if (P <= kPsisLdsPairs && psis_tail_lds_bytes(P) > 40 * 1024)
+      EXMC_KMAXLDS(psis_tail_kernel<true>, psis_tail_lds_bytes(P));
+    return EXMC_OK;
+  }
+};
+
+// the three launches over ll[S][Nb][C]; rows out[3][N], this block's datums from i0
+int psis_launch(hipStream_t stream, const PsisScratch& sc, const double* ll, int S, int Nb, int C, int N, int i0,
+                double* out) {
+  const long long n = (long long)S * C;
+  const IcGrid g = ic_grid(S, C, Nb);
+  if (sc.P <= kPsisLdsPairs) {
+    const size_t lds = psis_tail_lds_bytes(sc.P);
+    hipLaunchKernelGGL(psis_tail_kernel<true>, dim3((unsigned)Nb), dim3(kPsisBlock), lds, stream, ll, S, Nb, C, sc.M,
+                       sc.P, sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(), sc.meta.as<double>());
+  } else {
+    hipLaunchKernelGGL(psis_tail_kernel<false>, dim3((unsigned)Nb), dim3(kPsisBlock), 0, stream, ll, S, Nb, C, sc.M,
+                       sc.P, sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(), sc.meta.as<double>());
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(psis_weights_kernel, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks), dim3(g.block), 0, stream,
+                     ll, S, Nb, C, g.chunk, sc.P, sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(),
+                     sc.meta.as<double>(), sc.part.as<double>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(psis_merge_kernel, dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, stream,
+                     sc.part.as<double>(), g.n_chunks, n, Nb, sc.meta.as<double>(), N, i0, out);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+
+constexpr long long kPsisMaxSamples = 0x7FFFFFFFLL;   // sample indices are 32-bit in the tail tables
+
+// the model's datums in blocks whose matrix ll[S][Nb][C] fits scratch_bytes (one datum at the least)
+template <class Src>
+int psis_kind(exmc_hip_model* m, const Src& src, const double* draws, int S, int C, int N, size_t scratch_bytes,
+              double* out) {
+  const size_t per = (size_t)S * C * 8;
+  size_t fit = scratch_bytes / per;
+  const int Nb = (int)(fit < 1 ? 1 : (fit > (size_t)N ? (size_t)N : fit));
+  PsisScratch sc;
+  CallBuf ll;
+  int rc = sc.alloc(S, C, Nb);
+  if (!rc) rc = ll.alloc(per * Nb);
+  if (rc) return rc;
+  const size_t lds = ic_lds_bytes(m->d);
+  if (lds > 64 * 1024) EXMC_KMAXLDS(pointwise_ll_range_kernel<Src>, lds);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  for (int i0 = 0; i0 < N; i0 += Nb) {
+    const int nb = (N - i0 < Nb) ? N - i0 : Nb;
+    const IcGrid g = ic_grid(S, C, nb);
+    hipLaunchKernelGGL(pointwise_ll_range_kernel<Src>, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks),
+                       dim3(g.block), lds, m->stream, src, draws, S, m->d, C, i0, nb, g.chunk, ll.as<double>());
+    HIP_TRY(hipGetLastError());
+    rc = psis_launch(m->stream, sc, ll.as<double>(), S, nb, C, N, i0, out);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the kernels: before the scratch is freed
 }
 
 template <class Src>
@@ -2522,11 +2605,20 @@ int ic_launch(exmc_hip_model* m, const Src& src, bool matrix, const double* draw
   return finish_timing(m);   // waits for the kernels: before `part` is freed
 }
 
+// what ic_run does with the kind's source
+template <class Src>
+int ic_dispatch(exmc_hip_model* m, const Src& src, IcMode mode, size_t scratch_bytes, const double* draws, int S,
+                int C, int N, double* out) {
+  if (mode == kIcPsis) return psis_kind(m, src, draws, S, C, N, scratch_bytes, out);
+  return ic_launch(m, src, mode == kIcMatrix, draws, S, C, N, out);
+}
+
 #endif
 
 // the kind's source of ll over a device trace; simple, eight_schools and sv keep their data in
 // the handle's constants, uploaded here for the call
-int ic_run(exmc_hip_model* m, bool matrix, const double* draws, int S, int d, int C, double* out) {
+int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, int C, double* out,
+           size_t scratch_bytes = 0) {
   if (check_model(m)) return EXMC_ERR_BADARG;
   const int N = ic_n_data(m);
   if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
@@ -2534,9 +2626,11 @@ int ic_run(exmc_hip_model* m, bool matrix, const double* draws, int S, int d, in
     return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
   HIP_TRY(hipSetDevice(m->device));
 #ifdef EXMC_ONLY_CUSTOM
-  (void)matrix; (void)out;
+  (void)mode; (void)out; (void)scratch_bytes;
   return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
 #else
+  if (mode == kIcPsis && (long long)S * C > kPsisMaxSamples)
+    return fail(EXMC_ERR_BADARG, "psis: more than 2^31 - 1 pooled samples");
   const double l2p = log2pi32();
   std::vector<double> img;
   if (m->kind == EXMC_MODEL_SIMPLE) img.assign(m->sp.y, m->sp.y + m->sp.n);
@@ -2554,10 +2648,11 @@ int ic_run(exmc_hip_model* m, bool matrix, const double* draws, int S, int d, in
   int rc = EXMC_OK;
   switch (m->kind) {
     case EXMC_MODEL_SIMPLE:
-      rc = ic_launch(m, IcSimpleSrc{dimg.as<double>(), l2p, m->sp.tiny32}, matrix, draws, S, C, N, out);
+      rc = ic_dispatch(m, IcSimpleSrc{dimg.as<double>(), l2p, m->sp.tiny32}, mode, scratch_bytes, draws, S, C, N,
+                     out);
       break;
     case EXMC_MODEL_EIGHT_SCHOOLS:
-      rc = ic_launch(m, IcEightSchoolsSrc{dimg.as<double>(), l2p}, matrix, draws, S, C, N, out);
+      rc = ic_dispatch(m, IcEightSchoolsSrc{dimg.as<double>(), l2p}, mode, scratch_bytes, draws, S, C, N, out);
       break;
     case EXMC_MODEL_SV:
     case EXMC_MODEL_SV_NCP: {
@@ -2568,14 +2663,15 @@ int ic_run(exmc_hip_model* m, bool matrix, const double* draws, int S, int d, in
       src.pi32 = m->sv.pi32;
       src.tiny32 = m->sv.tiny32;
       src.ncp = m->kind == EXMC_MODEL_SV_NCP;
-      rc = ic_launch(m, src, matrix, draws, S, C, N, out);
+      rc = ic_dispatch(m, src, mode, scratch_bytes, draws, S, C, N, out);
       break;
     }
     case EXMC_MODEL_LOGISTIC:
-      rc = ic_launch(m, IcLogisticSrc{m->lg.X, m->lg.y, m->lg.lo, m->lg.hi}, matrix, draws, S, C, N, out);
+      rc = ic_dispatch(m, IcLogisticSrc{m->lg.X, m->lg.y, m->lg.lo, m->lg.hi}, mode, scratch_bytes, draws, S, C, N,
+                     out);
       break;
     case EXMC_MODEL_RADON:
-      rc = ic_launch(m, IcRadonSrc{m->rd.u, m->rd.cs, m->rd.fl, m->rd.y, m->rd.log2pi32, m->rd.tiny32}, matrix,
+      rc = ic_dispatch(m, IcRadonSrc{m->rd.u, m->rd.cs, m->rd.fl, m->rd.y, m->rd.log2pi32, m->rd.tiny32}, mode, scratch_bytes,
                      draws, S, C, N, out);
       break;
   }
@@ -2594,12 +2690,12 @@ int exmc_hip_model_n_data(const exmc_hip_model* m) {
 
 int exmc_hip_pointwise_loglik(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
                               double* ll_dev) {
-  return ic_run(m, true, draws_dev, n_draws, d, n_chains, ll_dev);
+  return ic_run(m, kIcMatrix, draws_dev, n_draws, d, n_chains, ll_dev);
 }
 
 int exmc_hip_ic_stats(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
                       double* stats_dev) {
-  return ic_run(m, false, draws_dev, n_draws, d, n_chains, stats_dev);
+  return ic_run(m, kIcStats, draws_dev, n_draws, d, n_chains, stats_dev);
 }
 
 int exmc_hip_ic_stats_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains,
@@ -2621,7 +2717,7 @@ int exmc_hip_ic_stats_host(exmc_hip_model* m, const double* draws_host, int n_dr
   if (rc) return rc;
   HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
   double* stats = buf.as<double>() + h.size();
-  rc = ic_run(m, false, buf.as<double>(), S, d, C, stats);
+  rc = ic_run(m, kIcStats, buf.as<double>(), S, d, C, stats);
   if (rc) return rc;
   HIP_TRY(hipMemcpy(stats_host, stats, (size_t)4 * N * 8, hipMemcpyDeviceToHost));
   return EXMC_OK;
@@ -2648,6 +2744,58 @@ int exmc_hip_ic_stats_from_ll(int device, const double* ll_dev, int n_draws, int
                      part.as<double>());
   HIP_TRY(hipGetLastError());
   rc = ic_merge((hipStream_t)0, part.as<double>(), g, (long long)S * C, N, stats_dev);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)0));
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_psis_stats(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
+                        size_t scratch_bytes, double* out_dev) {
+  return ic_run(m, kIcPsis, draws_dev, n_draws, d, n_chains, out_dev,
+                scratch_bytes ? scratch_bytes : (size_t)EXMC_PSIS_DEFAULT_SCRATCH);
+}
+
+int exmc_hip_psis_stats_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains,
+                             size_t scratch_bytes, double* out_host) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  const int N = ic_n_data(m);
+  if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
+  if (!draws_host || !out_host || d != m->d || n_draws < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
+    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  // [C][S][d] -> the device layout [S][d][C]
+  const int S = n_draws, C = n_chains;
+  std::vector<double> h((size_t)S * d * C);
+  for (int c = 0; c < C; c++)
+    for (int s = 0; s < S; s++)
+      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
+  CallBuf buf;
+  int rc = buf.alloc((h.size() + (size_t)3 * N) * 8);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  double* out = buf.as<double>() + h.size();
+  rc = exmc_hip_psis_stats(m, buf.as<double>(), S, d, C, scratch_bytes, out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(out_host, out, (size_t)3 * N * 8, hipMemcpyDeviceToHost));
+  return EXMC_OK;
+}
+
+int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, int n_data, int n_chains,
+                                double* out_dev) {
+  if (!ll_dev || !out_dev || n_draws < 1 || n_data < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
+    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  int rc = select_device(device);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  return fail(EXMC_ERR_UNSUPPORTED, "model comparison: use libexmc_hip.so for the model-free reduction");
+#else
+  if ((long long)n_draws * n_chains > kPsisMaxSamples)
+    return fail(EXMC_ERR_BADARG, "psis: more than 2^31 - 1 pooled samples");
+  PsisScratch sc;
+  rc = sc.alloc(n_draws, n_chains, n_data);
+  if (rc) return rc;
+  rc = psis_launch((hipStream_t)0, sc, ll_dev, n_draws, n_data, n_chains, n_data, 0, out_dev);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize((hipStream_t)0));
   return EXMC_OK;

@@ -270,10 +270,11 @@ __host__ __device__ inline size_t ic_lds_bytes(int d) {
 }
 
 // kOut = false: chunk partials [chunk][kIcFields][N] (ic_partials_kernel);
-// kOut = true: the matrix out[S][N][C] (pointwise_ll_kernel)
+// kOut = true: the matrix out[S][N][C] (pointwise_ll_kernel). The N datums are the model's datums
+// i0 .. i0 + N - 1 (pointwise_ll_range_kernel: a block of datums; i0 = 0 and all of them elsewhere).
 template <class Src, bool kOut>
 __device__ __forceinline__ void ic_body(const Src& src, const double* __restrict__ draws, int S, int d, int C,
-                                        int N, long long chunk, double* __restrict__ out) {
+                                        int N, long long chunk, double* __restrict__ out, int i0 = 0) {
   extern __shared__ double ic_lds[];
   const int ld = ic_ld(d);
   double* tile = ic_lds;
@@ -284,7 +285,7 @@ __device__ __forceinline__ void ic_body(const Src& src, const double* __restrict
   const long long n = (long long)S * C;
   const long long k0 = (long long)blockIdx.x * chunk;
   const long long k1 = (k0 + chunk < n) ? k0 + chunk : n;
-  typename Src::Datum dat = src.load(own ? i : 0);
+  typename Src::Datum dat = src.load(own ? i0 + i : 0);
   double st[kIcFields] = {-__builtin_inf(), 0.0, -__builtin_inf(), 0.0, 0.0, 0.0};
   for (long long kt = k0; kt < k1; kt += kIcTile) {
     const int nt = (int)((k1 - kt < kIcTile) ? k1 - kt : kIcTile);
@@ -346,6 +347,15 @@ __global__ __launch_bounds__(kIcBlock) void pointwise_ll_kernel(Src src, const d
                                                                int d, int C, int N, long long chunk,
                                                                double* __restrict__ ll) {
   ic_body<Src, true>(src, draws, S, d, C, N, chunk, ll);
+}
+
+// the matrix of the datums i0 .. i0 + Nb - 1 alone, out[S][Nb][C]: what PSIS-LOO (exmc_psis.hpp) walks
+// the model's datums in
+template <class Src>
+__global__ __launch_bounds__(kIcBlock) void pointwise_ll_range_kernel(Src src, const double* __restrict__ draws,
+                                                                     int S, int d, int C, int i0, int Nb,
+                                                                     long long chunk, double* __restrict__ ll) {
+  ic_body<Src, true>(src, draws, S, d, C, Nb, chunk, ll, i0);
 }
 
 #ifndef EXMC_ONLY_CUSTOM   // a generated model's plug-in carries no model-comparison kernels

@@ -4,6 +4,8 @@
     waic(compiled, draws)  -> {waic, elpd_waic, p_waic, se, n_obs, pointwise}   model_comparison.ex:63-84
     loo(compiled, draws)   -> {loo, elpd_loo, p_loo, se, n_obs, pointwise}      model_comparison.ex:95-114
     waic_from_pointwise(ll) / loo_from_pointwise(ll)  the same from a matrix [S][N][C]
+    psis_loo(compiled, draws) / psis_loo_from_pointwise(ll)  Pareto-smoothed LOO: loo's keys, plus
+                           pointwise["pareto_k"], k_threshold and n_high_k (DESIGN.md "PSIS-LOO")
     compare(results)       -> the results sorted by IC with d_elpd              model_comparison.ex:127-150
 
 The unit is the datum of a built-in kind (include/exmc_hip_compare.h, DESIGN.md "Model comparison"):
@@ -103,17 +105,22 @@ def pointwise_stats(compiled, draws):
     return res
 
 
-def _stats_from_ll(ll, device=None):
+def _ll_tensor(ll, device=None):
+    """a pointwise matrix [S][N][C] as a contiguous float64 device tensor"""
     import torch
     if isinstance(ll, torch.Tensor):
         if ll.dtype != torch.float64 or ll.dim() != 3 or not ll.is_cuda:
             raise ValueError("pointwise matrix must be a float64 CUDA tensor [S][N][C] or a host array")
-        x = ll.contiguous()
-    else:
-        a = np.asarray(ll, dtype=np.float64)
-        if a.ndim != 3:
-            raise ValueError("pointwise matrix must be [S][N][C]")
-        x = torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0 if device is None else device))
+        return ll.contiguous()
+    a = np.asarray(ll, dtype=np.float64)
+    if a.ndim != 3:
+        raise ValueError("pointwise matrix must be [S][N][C]")
+    return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0 if device is None else device))
+
+
+def _stats_from_ll(ll, device=None):
+    import torch
+    x = _ll_tensor(ll, device)
     S, N, C = x.shape
     if N < 1:
         raise ValueError("No observations for WAIC / LOO computation")
@@ -123,6 +130,39 @@ def _stats_from_ll(ll, device=None):
     _lib.check(_lib.load().exmc_hip_ic_stats_from_ll(x.device.index, x.data_ptr(), S, N, C, out.data_ptr()))
     torch.cuda.synchronize(x.device)
     return out.cpu().numpy()
+
+
+def psis_pointwise_stats(compiled, draws, scratch_bytes=0):
+    """PSIS-LOO per datum, [3][N] (elpd_loo, p_loo, Pareto k) in the CALLER's datum order, and the number of
+    pooled samples. The device walks the datums in blocks whose pointwise matrix fits scratch_bytes (0: the
+    library's default, 8 GiB); the result does not depend on it."""
+    import torch
+    N = n_data(compiled)
+    x = _device_trace(compiled, draws)
+    S, d, C = x.shape
+    _check_samples(S, C)
+    out = torch.empty((3, N), dtype=torch.float64, device=x.device)
+    _ordered_after_torch(x)
+    compiled.check(compiled.L.exmc_hip_psis_stats(compiled.h, x.data_ptr(), S, d, C, scratch_bytes, out.data_ptr()))
+    torch.cuda.synchronize(x.device)
+    st = out.cpu().numpy()
+    res = np.empty_like(st)
+    res[:, _datum_order(compiled, N)] = st
+    return res, S * C
+
+
+def _psis_from_ll(ll, device=None):
+    import torch
+    x = _ll_tensor(ll, device)
+    S, N, C = x.shape
+    if N < 1:
+        raise ValueError("No observations for WAIC / LOO computation")
+    _check_samples(S, C)
+    out = torch.empty((3, N), dtype=torch.float64, device=x.device)
+    _ordered_after_torch(x)
+    _lib.check(_lib.load().exmc_hip_psis_stats_from_ll(x.device.index, x.data_ptr(), S, N, C, out.data_ptr()))
+    torch.cuda.synchronize(x.device)
+    return out.cpu().numpy(), S * C
 
 
 def _variance(v):
@@ -196,6 +236,35 @@ def waic_from_pointwise(ll, names=None, device=None):
 def loo_from_pointwise(ll, names=None, device=None):
     st = _stats_from_ll(ll, device)
     return _loo_result(st, names if names is not None else list(range(st.shape[1])))
+
+
+def k_threshold(n):
+    """the sample-size dependent bound on a reliable Pareto k: min(1 - 1 / log10(n), 0.7)"""
+    return min(1.0 - 1.0 / math.log10(n), 0.7)
+
+
+def _psis_result(st, n, names):
+    r = loo_totals(st[0], st[1])
+    thr = k_threshold(n)
+    r["pointwise"] = dict(names=list(names), elpd_loo=st[0].copy(), p_loo=st[1].copy(), pareto_k=st[2].copy())
+    r["k_threshold"] = thr
+    r["n_high_k"] = int(np.sum(~(st[2] <= thr)))   # NaN (a degenerate fit, a non-finite term) counts
+    return r
+
+
+def psis_loo(compiled, draws, scratch_bytes=0):
+    """Pareto-smoothed importance-sampling LOO over the model's datums: loo's keys, the Pareto k of every
+    datum in pointwise["pareto_k"] (+inf where the tail is too short to fit: nothing was smoothed),
+    k_threshold and n_high_k, the number of datums whose k is not at or below it (above it, +inf, or NaN
+    from a degenerate fit: nothing vouches for their elpd_loo_i). A datum with a non-finite term has NaN in all three."""
+    st, n = psis_pointwise_stats(compiled, draws, scratch_bytes)
+    return _psis_result(st, n, datum_names(compiled))
+
+
+def psis_loo_from_pointwise(ll, names=None, device=None):
+    """psis_loo from a pointwise matrix [S][N][C] (device tensor or host array)"""
+    st, n = _psis_from_ll(ll, device)
+    return _psis_result(st, n, names if names is not None else list(range(st.shape[1])))
 
 
 def compare(results):

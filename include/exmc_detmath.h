@@ -276,6 +276,28 @@ EXMC_HD double exmc_log1p(double x) {
   return exmc_log(u) + (x - (u - 1.0)) / u;
 }
 
+/* expm1, for the generalised-Pareto quantile of PSIS-LOO (exmc_amd/csrc/exmc_psis.hpp). The same
+ * reduction and series as exp: x = k ln2 + r, expm1(r) = r + r^2 P(r) with P the exp polynomial
+ * without its two leading terms (1/2 + r/6 + ... + r^11/13!; the first term dropped, r^14/14!, is
+ * below 2^-56 |r|), then expm1(x) = 2^k expm1(r) + (2^k - 1) in one fma (2^k - 1 is exact for
+ * |k| <= 52). Above 40 the result is exp(x) - 1, below -40 it is -1 (the nearest double); NaN and
+ * a zero of either sign are returned as they are.
+ * Accuracy (tests/test_detmath_expm1.py, against math.expm1 over [-40, 40], dense around 0 and
+ * the reduction boundaries (k + 1/2) ln2): <= 2 ulp. */
+EXMC_HD double exmc_expm1(double x) {
+  if (!(x == x) || x == 0.0) return x;
+  if (x > 40.0) return exmc_exp(x) - 1.0;
+  if (x < -40.0) return -1.0;
+  const double kf = __builtin_rint(x * 0x1.71547652b82fep+0);
+  double r, p;
+  exmc_exp_core(kf, x, &r, &p);
+  p = __builtin_fma(p, r, 0.5);
+  const double e = __builtin_fma(r * r, p, r);
+  if (kf == 0.0) return e;
+  const double twok = exmc_from_bits((uint64_t)((int)kf + 1023) << 52);
+  return __builtin_fma(twok, e, twok - 1.0);
+}
+
 /* erf, for the generated TruncatedNormal term (lib/exmc/dist/truncated_normal.ex:27-40 calls Nx.erf,
  * which is :math.erf on BinaryBackend and XLA's own polynomial under EXLA: backend-defined like exp
  * and log, so this contract fixes one evaluation). No memorised coefficient table:

@@ -57,4 +57,7 @@ int exmc_hip_ic_stats_from_ll(int device, const double* ll_dev, int n_draws, int
 }
 #endif
 
+/* PSIS-LOO with the Pareto k diagnostic: the exmc_hip_psis_* entry points, part of this interface */
+#include "exmc_hip_psis.h"
+
 #endif
