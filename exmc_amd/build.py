@@ -8,8 +8,8 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "exmc_hip.hip")
 OUT_DIR = os.path.join(HERE, "lib")
 OUT = os.path.join(OUT_DIR, "libexmc_hip.so")
-# the model-independent kernels as an object of their own, linked into every plug-in library of a
-# generated model (exmc_amd/codegen.py build_plugin) instead of being compiled again with each
+# the model-free entry points and their kernels as an object of their own: compiled once, linked into
+# libexmc_hip.so and into every plug-in library of a generated model (exmc_amd/codegen.py build_plugin)
 COMMON_SRC = os.path.join(HERE, "csrc", "exmc_common.hip")
 COMMON_OBJ = os.path.join(OUT_DIR, "exmc_common.o")
 
@@ -21,6 +21,8 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_models.hpp"),
     os.path.join(HERE, "csrc", "exmc_device.hpp"),
     os.path.join(HERE, "csrc", "exmc_ess.hpp"),
+    os.path.join(HERE, "csrc", "exmc_diag.hpp"),
+    os.path.join(HERE, "csrc", "exmc_host.hpp"),
     os.path.join(HERE, "csrc", "exmc_ic.hpp"),
     os.path.join(HERE, "csrc", "exmc_psis.hpp"),
     os.path.join(HERE, "csrc", "exmc_plugin_part.hip"),
@@ -74,17 +76,28 @@ def build_common(force=False, verbose=False):
     return COMMON_OBJ
 
 
+def link_units(flags, src, common, out, verbose=False):
+    """`src` compiled with `flags` and linked with the object `common` into the shared library `out`."""
+    obj = "%s.%d.main.o" % (out, os.getpid())
+    cwd = os.path.join(HERE, "csrc")
+    try:
+        for cmd in ([hipcc()] + [f for f in flags if f != "-shared"] + ["-c", "-o", obj, src],
+                    [hipcc()] + [f for f in FLAGS if f in ("--offload-arch=gfx950", "-fPIC", "-shared")] + ["-o", out, obj, common]):
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd, cwd=cwd)
+    finally:
+        if os.path.exists(obj):
+            os.remove(obj)
+
+
 def build(force=False, verbose=False):
     if not force and up_to_date():
         build_common(verbose=verbose)
         return OUT
-    os.makedirs(OUT_DIR, exist_ok=True)
+    common = build_common(force=True, verbose=verbose)
     extra = os.environ.get("EXMC_EXTRA_FLAGS", "").split()
-    cmd = [hipcc()] + FLAGS + extra + ["-o", OUT, SRC]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd, cwd=os.path.join(HERE, "csrc"))
-    build_common(force=True, verbose=verbose)
+    link_units(FLAGS + extra, SRC, common, OUT, verbose)
     return OUT
 
 

@@ -1442,6 +1442,21 @@ def plugin_paths(gen):
     return d, os.path.join(d, "exmc_gen_model.h"), os.path.join(d, "libexmc_hip_gen.so")
 
 
+def _plugin_flags(hdr):
+    """(defines, compile flags, compile flags of host-side units) of a plug-in around the header `hdr`."""
+    defs = ["-DEXMC_ONLY_CUSTOM", '-DEXMC_CUSTOM_HEADER="%s"' % hdr]
+    flags = [f for f in _build.FLAGS if f != "-shared"] + _extra_flags()
+    return defs, flags, flags + ["-Xarch_host", "-O0"]   # launch code, nothing numeric
+
+
+def main_unit_cmd(hdr, obj, modules=True):
+    """The compile of a plug-in's main unit -- exmc_hip.hip around the header `hdr`, its model-dependent
+    kernels left to the parts -- to the object `obj`."""
+    defs, _, host_flags = _plugin_flags(hdr)
+    main_defs = ["-DEXMC_PLUGIN_SPLIT"] + (["-DEXMC_PLUGIN_MODULES"] if modules else [])
+    return [_build.hipcc()] + host_flags + defs + main_defs + ["-c", "-o", obj, _build.SRC]
+
+
 def build_plugin(gen, force=False, verbose=False):
     """hipcc the NUTS kernels around the generated functor (the analogue of the EXLA JIT step,
     jit.ex). Cached by the digest of the generated text and the kernel sources' mtimes."""
@@ -1457,16 +1472,12 @@ def build_plugin(gen, force=False, verbose=False):
             return so
     tmp = "%s.%d.tmp" % (so, os.getpid())       # two processes may build the same model: publish atomically
     hipcc = _build.hipcc()
-    defs = ["-DEXMC_ONLY_CUSTOM", '-DEXMC_CUSTOM_HEADER="%s"' % hdr]
-    flags = [f for f in _build.FLAGS if f != "-shared"] + _extra_flags()
+    defs, flags, host_flags = _plugin_flags(hdr)
     cwd = os.path.dirname(_build.SRC)
     objs = []
     try:
         if os.environ.get("EXMC_PLUGIN_ONE_TU") == "1":
-            cmd = [hipcc] + _build.FLAGS + _extra_flags() + defs + ["-o", tmp, _build.SRC]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd, cwd=cwd)
+            _build.link_units(flags + defs, _build.SRC, _build.build_common(), tmp, verbose)
         else:
             # The model-dependent kernels (sampling, its stream form, the two warmup forms, the four
             # auxiliary kernels) are compiled DEVICE-ONLY, one code object per part, side by side; the
@@ -1479,10 +1490,8 @@ def build_plugin(gen, force=False, verbose=False):
             # part a host + device unit launched through its stub).
             part_src = os.path.join(cwd, "exmc_plugin_part.hip")
             modules = os.environ.get("EXMC_PLUGIN_STUBS") != "1"
-            host_flags = flags + ["-Xarch_host", "-O0"]   # launch code, nothing numeric
             common = _build.build_common()
-            main_defs = ["-DEXMC_PLUGIN_SPLIT", "-DEXMC_COMMON_DECL_ONLY"] + (["-DEXMC_PLUGIN_MODULES"] if modules else [])
-            jobs = [([hipcc] + host_flags + defs + main_defs + ["-c", "-o", "%s.main.o" % tmp, _build.SRC])]
+            jobs = [main_unit_cmd(hdr, "%s.main.o" % tmp, modules)]
             layouts = [k for k, macro in ((1, "EXMC_GEN_ONE_LANE"), (2, "EXMC_GEN_VEC"), (3, "EXMC_GEN_LANES "))
                        if ("#define " + macro) in gen.header]
             parts = [(k, lay) for k in (3, 4, 7, 1, 2, 5) for lay in layouts]

@@ -1,8 +1,12 @@
-// exmc_hip.hip — C ABI of libexmc_hip.so (include/exmc_hip.h) over the gfx950 kernels.
-// Host control flow mirrors lib/exmc/nuts/sampler.ex (warmup schedule, dual averaging, Welford
-// mass matrix are plain Erlang-float code in the reference and plain C++ here); every leapfrog,
-// log-density, gradient, tree merge and U-turn test runs in the HIP kernels. There is no CPU
-// fallback: without a HIP device every compute entry point returns EXMC_ERR_NO_DEVICE.
+// exmc_hip.hip — the model-dependent half of the C ABI (include/exmc_hip.h): the handle, the layout
+// dispatch, sampling, warmup, model comparison. The entry points that name no model type -- the
+// native-tree seam, the fused-chain hook, the diagnostics launches, exmc_hip_last_error and
+// exmc_hip_device_count -- and their kernels are exmc_common.hip, which every library links
+// (exmc_host.hpp is the seam between the two). Every leapfrog, log-density, gradient, tree merge
+// and U-turn test runs in the HIP kernels, and so does the warmup of lib/exmc/nuts/sampler.ex
+// (window schedule, dual averaging, Welford mass matrix: warmup_kernel, exmc_nuts.hpp; the
+// host-driven form behind EXMC_HIP_HOST_WARMUP=1 restates the adaptation in plain C++ here). There
+// is no CPU fallback: without a HIP device every compute entry point returns EXMC_ERR_NO_DEVICE.
 #include "../../include/exmc_hip.h"
 #include "../../include/exmc_hip_compare.h"
 
@@ -22,11 +26,12 @@
 
 #include "../../include/exmc_zig_tables.h"
 #include "exmc_kernels.hpp"
-#include "exmc_native_tree.hpp"
+#include "exmc_host.hpp"
 #include "exmc_ic.hpp"
 #include "exmc_psis.hpp"
 
 using namespace exmc;
+using namespace exmc::host;
 
 #ifdef EXMC_PLUGIN_SPLIT
 // a plug-in built in parts (exmc_plugin_part.hip): the four heavy kernels are compiled in translation
@@ -62,46 +67,10 @@ hipError_t print_sections(const char* what, double ms) {
 #endif
 
 
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(EXMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
-
 const uint64_t kZigKi[256] = EXMC_ZIG_KI_INIT;
 const double kZigWi[256] = EXMC_ZIG_WI_INIT;
 const double kZigFi[256] = EXMC_ZIG_FI_INIT;
 
-double f32r(double x) { return (double)(float)x; }
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return EXMC_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(&p, bytes));
-    cap = bytes;
-    return EXMC_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
 
 // ---- launching the model-dependent kernels --------------------------------------------------
 // libexmc_hip.so and one-unit plug-ins: the kernel is an instantiation of this translation unit,
@@ -1090,8 +1059,6 @@ int check_model(const exmc_hip_model* m) {
 // (eight_schools, simple, generated models) or the caller's to state (radon).
 using Names = std::vector<std::string>;
 
-double log2pi32() { return f32r(std::log(f32r(2.0 * M_PI))); }
-
 int upload_image(exmc_hip_model* m, const std::vector<double>& image) {
   int rc = m->data.ensure(image.size() * 8);
   if (rc) return rc;
@@ -1293,14 +1260,6 @@ int create_kind(exmc_hip_model* m, const double* data, int n_data, Names& names)
 
 // =========================================== C ABI ==========================================
 extern "C" {
-
-const char* exmc_hip_last_error(void) { return g_last_error.c_str(); }
-
-int exmc_hip_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
 
 int exmc_hip_model_create(int kind, int d, const double* data, int n_data, int device,
                           exmc_hip_model** out) {
@@ -1910,117 +1869,6 @@ int exmc_hip_stream_finish(exmc_hip_model* m, int32_t* divergences) {
   return EXMC_OK;
 }
 
-int exmc_hip_build_full_tree_host(int device, int C, int d, const double* q0, const double* p0,
-                                  const double* g0, const double* logp0, const double* fwd_q,
-                                  const double* fwd_p, const double* fwd_logp, const double* fwd_g,
-                                  int n_fwd, const double* bwd_q, const double* bwd_p,
-                                  const double* bwd_logp, const double* bwd_g, int n_bwd,
-                                  const double* inv_mass, const double* jlp0, int max_depth,
-                                  const uint64_t* seeds, double* q_out, double* logp_out,
-                                  double* g_out, int32_t* n_steps, int32_t* divergent,
-                                  double* accept_sum, int32_t* depth) {
-  if (C < 1 || d < 1 || n_fwd < 0 || n_bwd < 0 || max_depth < 0 || max_depth > kFtLevels ||
-      !q0 || !p0 || !g0 || !logp0 || !inv_mass || !jlp0 || !seeds || !q_out || !logp_out ||
-      !g_out || !n_steps || !divergent || !accept_sum || !depth ||
-      (n_fwd > 0 && (!fwd_q || !fwd_p || !fwd_logp || !fwd_g)) ||
-      (n_bwd > 0 && (!bwd_q || !bwd_p || !bwd_logp || !bwd_g)))
-    return fail(EXMC_ERR_BADARG, "bad arguments");   // NifResult badarg (lib.rs)
-  int ndev = exmc_hip_device_count();
-  if (ndev <= 0)
-    return fail(EXMC_ERR_NO_DEVICE, "no HIP device visible: libexmc_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(EXMC_ERR_BADARG, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
-  const size_t vec = (size_t)C * d, fw = (size_t)C * n_fwd * d, bw = (size_t)C * n_bwd * d;
-  // one device arena: inputs, scratch, outputs (doubles), then int32 outputs
-  const size_t n_in = 3 * vec + C + 3 * fw + (size_t)C * n_fwd + 3 * bw + (size_t)C * n_bwd + d + C + C;
-  const size_t n_scr = (size_t)C * (kFtLevels + 3) * d;
-  const size_t n_out = 2 * vec + 2 * (size_t)C;
-  const size_t total = (n_in + n_scr + n_out) * 8 + 3 * (size_t)C * 4;
-  DevBuf arena;
-  int rc = arena.ensure(total);
-  if (rc) return rc;
-  double* b = arena.as<double>();
-  FullTreeParams P;
-  P.n_chains = C; P.d = d; P.n_fwd = n_fwd; P.n_bwd = n_bwd; P.max_depth = max_depth;
-  std::vector<std::pair<const void*, size_t>> ups;
-  auto put = [&](const double* src, size_t n) {
-    double* dst = b;
-    if (n) ups.push_back({src, n});
-    b += n;
-    return (const double*)dst;
-  };
-  P.q0 = put(q0, vec); P.p0 = put(p0, vec); P.g0 = put(g0, vec); P.logp0 = put(logp0, C);
-  P.fwd_q = put(fwd_q, fw); P.fwd_p = put(fwd_p, fw); P.fwd_g = put(fwd_g, fw);
-  P.fwd_logp = put(fwd_logp, (size_t)C * n_fwd);
-  P.bwd_q = put(bwd_q, bw); P.bwd_p = put(bwd_p, bw); P.bwd_g = put(bwd_g, bw);
-  P.bwd_logp = put(bwd_logp, (size_t)C * n_bwd);
-  P.inv_mass = put(inv_mass, d); P.jlp0 = put(jlp0, C);
-  P.seeds = (const uint64_t*)put((const double*)seeds, C);
-  {
-    double* dst = arena.as<double>();
-    for (auto& u : ups) {
-      if (hipMemcpy(dst, u.first, u.second * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        arena.release();
-        return fail(EXMC_ERR_HIP, "upload failed");
-      }
-      dst += u.second;
-    }
-  }
-  P.scratch = b; b += n_scr;
-  P.out_q = b; b += vec;
-  P.out_g = b; b += vec;
-  P.out_logp = b; b += C;
-  P.out_accept_sum = b; b += C;
-  int32_t* ib = (int32_t*)b;
-  P.out_n_steps = ib; P.out_divergent = ib + C; P.out_depth = ib + 2 * (size_t)C;
-  hipLaunchKernelGGL(full_tree_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, 0, P);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(q_out, P.out_q, vec * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(g_out, P.out_g, vec * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(logp_out, P.out_logp, (size_t)C * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(accept_sum, P.out_accept_sum, (size_t)C * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(n_steps, P.out_n_steps, (size_t)C * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(divergent, P.out_divergent, (size_t)C * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(depth, P.out_depth, (size_t)C * 4, hipMemcpyDeviceToHost);
-  arena.release();
-  if (e != hipSuccess) return fail(EXMC_ERR_HIP, std::string("build_full_tree: ") + hipGetErrorString(e));
-  return EXMC_OK;
-}
-
-namespace {
-// Diagnostics.ess of every series of a [S][D][C] device array: one lane per series up to lag 15,
-// then a wavefront per unfinished series (ess_tail_kernel needs the series in LDS; longer ones
-// stay with their lane to the end)
-int launch_ess(exmc_hip_model* m, const double* src, int n_draws, int d, int n_chains, double* ess_dev) {
-  const size_t series = (size_t)d * n_chains;
-  const dim3 grid((unsigned)((series + kEssBlock - 1) / kEssBlock));
-  const size_t lds = (size_t)n_draws * 8;
-  if (lds > 160 * 1024) {
-    hipLaunchKernelGGL(ess_series_kernel, grid, dim3(kEssBlock), 0, m->stream, src, n_draws, d, n_chains,
-                       ess_dev, (int*)nullptr, (EssTailItem*)nullptr);
-    HIP_TRY(hipGetLastError());
-    return EXMC_OK;
-  }
-  int rc = m->esswork.ensure(16 + series * sizeof(EssTailItem));
-  if (rc) return rc;
-  int* count = (int*)m->esswork.p;
-  EssTailItem* items = (EssTailItem*)((char*)m->esswork.p + 16);
-  HIP_TRY(hipMemsetAsync(count, 0, 16, m->stream));
-  hipLaunchKernelGGL(ess_series_kernel, grid, dim3(kEssBlock), 0, m->stream, src, n_draws, d, n_chains,
-                     ess_dev, count, items);
-  HIP_TRY(hipGetLastError());
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void*)ess_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  const unsigned tail_blocks = (unsigned)(series < 2048 ? series : 2048);
-  hipLaunchKernelGGL(ess_tail_kernel, dim3(tail_blocks), dim3(64), lds, m->stream, src, n_draws, d,
-                     n_chains, ess_dev, (const int*)count, (const EssTailItem*)items);
-  HIP_TRY(hipGetLastError());
-  return EXMC_OK;
-}
-}  // namespace
-
 int exmc_hip_ess(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
                  double* ess_dev) {
   if (check_model(m)) return EXMC_ERR_BADARG;
@@ -2028,7 +1876,7 @@ int exmc_hip_ess(exmc_hip_model* m, const double* draws_dev, int n_draws, int d,
     return fail(EXMC_ERR_BADARG, "bad arguments");
   HIP_TRY(hipSetDevice(m->device));
   HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  int rc = launch_ess(m, draws_dev, n_draws, d, n_chains, ess_dev);
+  int rc = launch_ess(m->stream, m->esswork, draws_dev, n_draws, d, n_chains, ess_dev);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
   return finish_timing(m);
@@ -2040,29 +1888,15 @@ int exmc_hip_ess_bulk(exmc_hip_model* m, const double* draws_dev, int n_draws, i
   if (!draws_dev || !ess_dev || n_draws < 1 || d < 1 || n_chains < 1)
     return fail(EXMC_ERR_BADARG, "bad arguments");
   if (n_draws < 4) return exmc_hip_ess(m, draws_dev, n_draws, d, n_chains, ess_dev);   // diagnostics.ex:62
-  const size_t lds = (size_t)n_draws * 8;
-  if (lds > 160 * 1024) return fail(EXMC_ERR_UNSUPPORTED, "n_draws too large for the LDS rank kernel (max 20480)");
+  if ((size_t)n_draws * 8 > 160 * 1024)
+    return fail(EXMC_ERR_UNSUPPORTED, "n_draws too large for the LDS rank kernel (max 20480)");
   HIP_TRY(hipSetDevice(m->device));
-  const size_t series = (size_t)d * n_chains;
-  int rc = m->scores.ensure(series * (size_t)n_draws * 8);   // the normal scores, [S][D][C]
+  int rc = m->scores.ensure((size_t)d * n_chains * (size_t)n_draws * 8);   // the normal scores, [S][D][C]
+  if (!rc) rc = rank_scores_lds(n_draws);
   if (rc) return rc;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void*)rank_scores_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  int P = 2;
-  while (P < n_draws) P <<= 1;
-  const char* re = std::getenv("EXMC_HIP_RANK_SORT");   // 0: the counting kernel (A/B runs, tests)
-  if (P <= kRankSortMaxP && !(re && re[0] == '0')) {
-    // ranks by sorting the series in LDS (exmc_kernels.hpp rank_scores_sort_kernel)
-    hipLaunchKernelGGL(rank_scores_sort_kernel, dim3((unsigned)series), dim3(256), (size_t)P * 12, m->stream,
-                       draws_dev, n_draws, P, d, n_chains, m->scores.as<double>());
-  } else {
-    hipLaunchKernelGGL(rank_scores_kernel, dim3((unsigned)series), dim3(256), lds, m->stream,
-                       draws_dev, n_draws, d, n_chains, m->scores.as<double>());
-  }
-  HIP_TRY(hipGetLastError());
-  rc = launch_ess(m, (const double*)m->scores.as<double>(), n_draws, d, n_chains, ess_dev);
+  rc = launch_rank_scores(m->stream, draws_dev, n_draws, d, n_chains, m->scores.as<double>());
+  if (!rc) rc = launch_ess(m->stream, m->esswork, m->scores.as<double>(), n_draws, d, n_chains, ess_dev);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
   return finish_timing(m);
@@ -2077,362 +1911,10 @@ int exmc_hip_rhat(exmc_hip_model* m, const double* draws_dev, int n_draws, int d
   int rc = m->io.ensure((size_t)d * 4 * n_chains * 8);   // half-chain means and variances
   if (rc) return rc;
   HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  const unsigned slices = (unsigned)((2 * n_chains + 255) / 256);
-  hipLaunchKernelGGL(rhat_kernel, dim3((unsigned)d, slices), dim3(256), 0, m->stream, draws_dev,
-                     n_draws, d, n_chains, m->io.as<double>(), rhat_dev, 0);
-  hipLaunchKernelGGL(rhat_kernel, dim3((unsigned)d), dim3(64), 0, m->stream, draws_dev, n_draws, d,
-                     n_chains, m->io.as<double>(), rhat_dev, 1);
-  HIP_TRY(hipGetLastError());
+  rc = launch_rhat(m->stream, draws_dev, n_draws, d, n_chains, m->io.as<double>(), rhat_dev);
+  if (rc) return rc;
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
   return finish_timing(m);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// The NIF's incremental trajectory interface, batched (include/exmc_hip.h; kernels in
-// exmc_native_tree.hpp). Blocking calls on the null stream: the interface is a compatibility
-// seam (one call per doubling), not a throughput path.
-// ------------------------------------------------------------------------------------------
-struct exmc_hip_traj {
-  int device = 0, C = 0, d = 0;
-  DevBuf state;
-  TrajDev T{};
-};
-
-namespace {
-
-// carve a TrajDev out of one allocation: 9 vectors [C][d], 3 scalars [C], 4 int32 [C]
-size_t traj_bytes(int C, int d) { return ((size_t)9 * C * d + 3 * (size_t)C) * 8 + 4 * (size_t)C * 4; }
-TrajDev traj_view(void* base, int C, int d) {
-  TrajDev t;
-  double* b = (double*)base;
-  const size_t v = (size_t)C * d;
-  t.qL = b; t.pL = b + v; t.gL = b + 2 * v; t.qR = b + 3 * v; t.pR = b + 4 * v; t.gR = b + 5 * v;
-  t.qP = b + 6 * v; t.gP = b + 7 * v; t.rho = b + 8 * v;
-  b += 9 * v;
-  t.logpP = b; t.lsw = b + C; t.acc = b + 2 * (size_t)C;
-  int32_t* ib = (int32_t*)(b + 3 * (size_t)C);
-  t.n = ib; t.depth = ib + C; t.div = ib + 2 * (size_t)C; t.turn = ib + 3 * (size_t)C;
-  return t;
-}
-
-int select_device(int device) {
-  const int ndev = exmc_hip_device_count();
-  if (ndev <= 0)
-    return fail(EXMC_ERR_NO_DEVICE, "no HIP device visible: libexmc_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(EXMC_ERR_BADARG, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
-  return EXMC_OK;
-}
-
-// uploads of one subtree call: the four state arrays, inv_mass and the per-chain scalars
-struct SubtreeUpload {
-  DevBuf buf;
-  SubtreeParams P{};
-  int fill(int C, int d, const double* all_q, const double* all_p, const double* all_logp,
-           const double* all_g, int n_states, const double* inv_mass, const double* jlp0,
-           const int32_t* depth, const int32_t* go_right, const uint64_t* seeds) {
-    if (C < 1 || d < 1 || n_states < 1 || !all_q || !all_p || !all_logp || !all_g || !inv_mass ||
-        !jlp0 || !depth || !go_right || !seeds)
-      return fail(EXMC_ERR_BADARG, "bad arguments");
-    for (int c = 0; c < C; c++)
-      if (depth[c] >= kFtLevels || (depth[c] >= 0 && ((size_t)1 << depth[c]) > (size_t)n_states))
-        return fail(EXMC_ERR_BADARG, "depth needs more pre-computed states than were passed");
-    const size_t st = (size_t)C * n_states * d, sc = (size_t)C * n_states;
-    const size_t nd = 3 * st + sc + d + C /*jlp0*/ + C /*seeds*/ + (size_t)C * (kFtLevels + 2) * d;
-    int rc = buf.ensure(nd * 8 + 2 * (size_t)C * 4);
-    if (rc) return rc;
-    double* b = buf.as<double>();
-    auto up = [&](const void* src, size_t n_doubles) -> const double* {
-      double* dst = b;
-      if (hipMemcpy(dst, src, n_doubles * 8, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-      b += n_doubles;
-      return dst;
-    };
-    P.n_chains = C; P.d = d; P.n_states = n_states;
-    P.all_q = up(all_q, st); P.all_p = up(all_p, st); P.all_g = up(all_g, st);
-    P.all_logp = up(all_logp, sc);
-    P.inv_mass = up(inv_mass, d); P.jlp0 = up(jlp0, C);
-    P.seeds = (const uint64_t*)up(seeds, C);
-    P.scratch = b; b += (size_t)C * (kFtLevels + 2) * d;
-    int32_t* ib = (int32_t*)b;
-    if (!P.all_q || !P.all_p || !P.all_g || !P.all_logp || !P.inv_mass || !P.jlp0 || !P.seeds ||
-        hipMemcpy(ib, depth, (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ib + C, go_right, (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(EXMC_ERR_HIP, "upload failed");
-    P.depth = ib; P.go_right = ib + C;
-    return EXMC_OK;
-  }
-};
-
-// scratch of exmc_hip_leapfrog_chain_normal_host (see there), one per device, never freed
-struct ChainScratch {
-  std::mutex mu;
-  void* dev = nullptr;
-  void* host = nullptr;
-};
-constexpr size_t kChainScratchBytes = (size_t)8 << 20;
-constexpr int kChainScratchDevices = 16;
-constexpr size_t kChainZeroCopyBytes = (size_t)1 << 20;   // rows the kernel writes straight into the staging buffer
-ChainScratch g_chain_scratch[kChainScratchDevices];
-
-int down(void* dst, const void* src, size_t bytes) {
-  if (!dst) return EXMC_OK;
-  HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-  return EXMC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int exmc_hip_traj_create(int device, int C, int d, const double* q, const double* p,
-                         const double* grad, const double* logp, exmc_hip_traj** out) {
-  if (!out || C < 1 || d < 1 || !q || !p || !grad || !logp) return fail(EXMC_ERR_BADARG, "bad arguments");
-  *out = nullptr;
-  int rc = select_device(device);
-  if (rc) return rc;
-  exmc_hip_traj* t = new exmc_hip_traj();
-  t->device = device; t->C = C; t->d = d;
-  rc = t->state.ensure(traj_bytes(C, d));
-  if (rc) { delete t; return rc; }
-  t->T = traj_view(t->state.p, C, d);
-  const size_t v = (size_t)C * d * 8;
-  hipError_t e = hipMemset(t->state.p, 0, traj_bytes(C, d));   // lsw, acc, n, depth, div, turn = 0
-  // Trajectory::new (types.rs:136-152): both endpoints and the proposal are the start state, rho = p
-  const double* src[9] = {q, p, grad, q, p, grad, q, grad, p};
-  double* dst[9] = {t->T.qL, t->T.pL, t->T.gL, t->T.qR, t->T.pR, t->T.gR, t->T.qP, t->T.gP, t->T.rho};
-  for (int i = 0; i < 9 && e == hipSuccess; i++) e = hipMemcpy(dst[i], src[i], v, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(t->T.logpP, logp, (size_t)C * 8, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    t->state.release();
-    delete t;
-    return fail(EXMC_ERR_HIP, std::string("traj_create: ") + hipGetErrorString(e));
-  }
-  *out = t;
-  return EXMC_OK;
-}
-
-void exmc_hip_traj_destroy(exmc_hip_traj* t) {
-  if (!t) return;
-  (void)hipSetDevice(t->device);
-  t->state.release();
-  delete t;
-}
-
-int exmc_hip_traj_get_endpoint_host(exmc_hip_traj* t, const int32_t* go_right, double* q, double* p,
-                                    double* grad) {
-  if (!t || !go_right || !q || !p || !grad) return fail(EXMC_ERR_BADARG, "bad arguments");
-  HIP_TRY(hipSetDevice(t->device));
-  const size_t row = (size_t)t->d * 8;
-  for (int c = 0; c < t->C; c++) {
-    const size_t o = (size_t)c * t->d;
-    const bool r = go_right[c] != 0;
-    HIP_TRY(hipMemcpy(q + o, (r ? t->T.qR : t->T.qL) + o, row, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(p + o, (r ? t->T.pR : t->T.pL) + o, row, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(grad + o, (r ? t->T.gR : t->T.gL) + o, row, hipMemcpyDeviceToHost));
-  }
-  return EXMC_OK;
-}
-
-int exmc_hip_traj_build_and_merge_host(exmc_hip_traj* t, const double* all_q, const double* all_p,
-                                       const double* all_logp, const double* all_grad,
-                                       int n_states, const double* inv_mass, const double* jlp0,
-                                       const int32_t* depth, const int32_t* go_right,
-                                       const uint64_t* seeds) {
-  if (!t) return fail(EXMC_ERR_BADARG, "bad arguments");
-  HIP_TRY(hipSetDevice(t->device));
-  SubtreeUpload u;
-  int rc = u.fill(t->C, t->d, all_q, all_p, all_logp, all_grad, n_states, inv_mass, jlp0, depth,
-                  go_right, seeds);
-  if (rc == EXMC_OK) {
-    u.P.T = t->T;
-    hipLaunchKernelGGL(traj_build_and_merge_kernel, dim3((unsigned)((t->C + 63) / 64)), dim3(64), 0,
-                       0, u.P);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) rc = fail(EXMC_ERR_HIP, std::string("build_and_merge: ") + hipGetErrorString(e));
-  }
-  u.buf.release();
-  return rc;
-}
-
-int exmc_hip_traj_is_terminated_host(exmc_hip_traj* t, int32_t* out) {
-  if (!t || !out) return fail(EXMC_ERR_BADARG, "bad arguments");
-  HIP_TRY(hipSetDevice(t->device));
-  std::vector<int32_t> dv(t->C), tn(t->C);
-  HIP_TRY(hipMemcpy(dv.data(), t->T.div, (size_t)t->C * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(tn.data(), t->T.turn, (size_t)t->C * 4, hipMemcpyDeviceToHost));
-  for (int c = 0; c < t->C; c++) out[c] = (dv[c] || tn[c]) ? 1 : 0;   // types.rs:160-162
-  return EXMC_OK;
-}
-
-int exmc_hip_traj_get_result_host(exmc_hip_traj* t, double* q, double* logp, double* grad,
-                                  int32_t* n_steps, int32_t* divergent, double* accept_sum,
-                                  int32_t* depth) {
-  if (!t) return fail(EXMC_ERR_BADARG, "bad arguments");
-  HIP_TRY(hipSetDevice(t->device));
-  const size_t v = (size_t)t->C * t->d * 8, s8 = (size_t)t->C * 8, s4 = (size_t)t->C * 4;
-  int rc = down(q, t->T.qP, v);
-  if (!rc) rc = down(grad, t->T.gP, v);
-  if (!rc) rc = down(logp, t->T.logpP, s8);
-  if (!rc) rc = down(accept_sum, t->T.acc, s8);
-  if (!rc) rc = down(n_steps, t->T.n, s4);
-  if (!rc) rc = down(divergent, t->T.div, s4);
-  if (!rc) rc = down(depth, t->T.depth, s4);
-  return rc;
-}
-
-int exmc_hip_build_subtree_host(int device, int C, int d, const double* all_q, const double* all_p,
-                                const double* all_logp, const double* all_grad, int n_states,
-                                const double* inv_mass, const double* jlp0, const int32_t* depth,
-                                const int32_t* going_right, const uint64_t* seeds, double* q_left,
-                                double* p_left, double* grad_left, double* q_right, double* p_right,
-                                double* grad_right, double* q_prop, double* logp_prop,
-                                double* grad_prop, double* log_sum_weight, int32_t* n_steps,
-                                int32_t* divergent, double* accept_sum, int32_t* turning,
-                                int32_t* subtree_depth, double* rho) {
-  int rc = select_device(device);
-  if (rc) return rc;
-  SubtreeUpload u;
-  rc = u.fill(C, d, all_q, all_p, all_logp, all_grad, n_states, inv_mass, jlp0, depth, going_right,
-              seeds);
-  DevBuf outb;
-  if (rc == EXMC_OK) rc = outb.ensure(traj_bytes(C, d));
-  if (rc == EXMC_OK) {
-    u.P.out = traj_view(outb.p, C, d);
-    hipError_t e = hipMemset(outb.p, 0, traj_bytes(C, d));
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(build_subtree_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, 0, u.P);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) rc = fail(EXMC_ERR_HIP, std::string("build_subtree: ") + hipGetErrorString(e));
-  }
-  if (rc == EXMC_OK) {
-    const TrajDev& o = u.P.out;
-    const size_t v = (size_t)C * d * 8, s8 = (size_t)C * 8, s4 = (size_t)C * 4;
-    const std::pair<void*, const void*> vec[9] = {{q_left, o.qL}, {p_left, o.pL}, {grad_left, o.gL},
-                                                  {q_right, o.qR}, {p_right, o.pR}, {grad_right, o.gR},
-                                                  {q_prop, o.qP}, {grad_prop, o.gP}, {rho, o.rho}};
-    for (int i = 0; i < 9 && !rc; i++) rc = down(vec[i].first, vec[i].second, v);
-    if (!rc) rc = down(logp_prop, o.logpP, s8);
-    if (!rc) rc = down(log_sum_weight, o.lsw, s8);
-    if (!rc) rc = down(accept_sum, o.acc, s8);
-    if (!rc) rc = down(n_steps, o.n, s4);
-    if (!rc) rc = down(divergent, o.div, s4);
-    if (!rc) rc = down(turning, o.turn, s4);
-    if (!rc) rc = down(subtree_depth, o.depth, s4);
-  }
-  u.buf.release();
-  outb.release();
-  return rc;
-}
-
-// B2' (tree.ex:613-653): see leapfrog_chain_normal_kernel. Blocking, on the null stream, like the other
-// handle-less seams: the reference's hook uploads, dispatches and downloads per call as well. The hook exists
-// to cut the cost of a DISPATCH (tree.ex:613-619), so a call of ordinary size pays for no allocation: a scratch
-// per device (device buffer + page-locked staging, kChainScratchBytes each, made on first use and kept), ONE
-// packed upload (q, p, inv_mass) and ONE packed download (the three row sets and logp) -- and up to 1 MB of rows no
-// copy at all (the kernel works on the staging buffer itself). Calls on a device are
-// serialised by its scratch's lock (they share the null stream anyway). Larger batches allocate and free.
-int exmc_hip_leapfrog_chain_normal_host(int device, int C, int d, const double* q, const double* p,
-                                        const double* inv_mass, int k, double signed_eps, double mu,
-                                        double sigma, double* q_chain, double* p_chain,
-                                        double* grad_chain, double* logp_chain) {
-  if (C < 1 || d < 1 || d > kChainNormalMaxD || k < 0 || !q || !p || !inv_mass)
-    return fail(EXMC_ERR_BADARG, "leapfrog_chain_normal: need n_chains >= 1, 1 <= d <= 256, k >= 0 and q, p, inv_mass");
-  int rc = select_device(device);
-  if (rc) return rc;
-  if (k == 0) return EXMC_OK;
-  const size_t vec = (size_t)C * d, rows = (size_t)C * k * d, lps = (size_t)C * k;
-  const size_t n_in = 2 * vec + (size_t)d, n_out = 3 * rows + lps;
-  const bool cached = (n_in + n_out) * 8 <= kChainScratchBytes && device < kChainScratchDevices;
-  ChainScratch* sc = cached ? &g_chain_scratch[device] : nullptr;
-  std::unique_lock<std::mutex> lock;
-  DevBuf buf;
-  double* dbase = nullptr;
-  double* hbase = nullptr;
-  if (sc) {
-    lock = std::unique_lock<std::mutex>(sc->mu);
-    if (!sc->dev) HIP_TRY(hipMalloc(&sc->dev, kChainScratchBytes));
-    if (!sc->host) HIP_TRY(hipHostMalloc(&sc->host, kChainScratchBytes, hipHostMallocDefault));
-    dbase = (double*)sc->dev;
-    hbase = (double*)sc->host;
-  } else {
-    rc = buf.ensure((n_in + n_out) * 8);
-    if (rc) return rc;
-    dbase = (double*)buf.p;
-  }
-  ChainNormalParams P{};
-  P.q = dbase; P.p = dbase + vec; P.inv_mass = dbase + 2 * vec;
-  P.d = d; P.k = k; P.n_chains = C;
-  P.eps = signed_eps; P.mu = mu; P.sigma = sigma;
-  P.tiny32 = f32r(1.0e-30);
-  P.log2pi32 = f32r(std::log(f32r(2.0 * M_PI)));
-  P.q_chain = dbase + n_in;
-  P.p_chain = P.q_chain + rows;
-  P.g_chain = P.p_chain + rows;
-  P.logp_chain = P.g_chain + rows;
-  hipError_t e;
-  // a call of ordinary size (the reference's: one chain, K = 32) moves so little that the two copies cost more
-  // than the kernel: it reads its inputs from, and writes its rows to, the page-locked staging directly (the
-  // buffer is device-accessible; the kernel's end makes the rows visible to the host) -- no copy kernels at all
-  const bool zero_copy = hbase && n_out * 8 <= kChainZeroCopyBytes;
-  if (zero_copy) {
-    std::memcpy(hbase, q, vec * 8);
-    std::memcpy(hbase + vec, p, vec * 8);
-    std::memcpy(hbase + 2 * vec, inv_mass, (size_t)d * 8);
-    P.q = hbase; P.p = hbase + vec; P.inv_mass = hbase + 2 * vec;
-    P.q_chain = hbase + n_in;
-    P.p_chain = P.q_chain + rows;
-    P.g_chain = P.p_chain + rows;
-    P.logp_chain = P.g_chain + rows;
-    hipLaunchKernelGGL(leapfrog_chain_normal_kernel, dim3((unsigned)C), dim3(64), 0, 0, P);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return fail(EXMC_ERR_HIP, std::string("leapfrog_chain_normal: ") + hipGetErrorString(e));
-    const double* o = hbase + n_in;
-    if (q_chain) std::memcpy(q_chain, o, rows * 8);
-    if (p_chain) std::memcpy(p_chain, o + rows, rows * 8);
-    if (grad_chain) std::memcpy(grad_chain, o + 2 * rows, rows * 8);
-    if (logp_chain) std::memcpy(logp_chain, o + 3 * rows, lps * 8);
-    return EXMC_OK;
-  }
-  if (hbase) {
-    std::memcpy(hbase, q, vec * 8);
-    std::memcpy(hbase + vec, p, vec * 8);
-    std::memcpy(hbase + 2 * vec, inv_mass, (size_t)d * 8);
-    e = hipMemcpy(dbase, hbase, n_in * 8, hipMemcpyHostToDevice);
-  } else {
-    e = hipMemcpy(dbase, q, vec * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dbase + vec, p, vec * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dbase + 2 * vec, inv_mass, (size_t)d * 8, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(leapfrog_chain_normal_kernel, dim3((unsigned)C), dim3(64), 0, 0, P);
-    e = hipGetLastError();
-  }
-  if (hbase) {
-    // the blocking copy waits for the kernel (same stream)
-    if (e == hipSuccess) e = hipMemcpy(hbase + n_in, P.q_chain, n_out * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(EXMC_ERR_HIP, std::string("leapfrog_chain_normal: ") + hipGetErrorString(e));
-    const double* o = hbase + n_in;
-    if (q_chain) std::memcpy(q_chain, o, rows * 8);
-    if (p_chain) std::memcpy(p_chain, o + rows, rows * 8);
-    if (grad_chain) std::memcpy(grad_chain, o + 2 * rows, rows * 8);
-    if (logp_chain) std::memcpy(logp_chain, o + 3 * rows, lps * 8);
-    return EXMC_OK;
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) rc = fail(EXMC_ERR_HIP, std::string("leapfrog_chain_normal: ") + hipGetErrorString(e));
-  if (!rc) rc = down(q_chain, P.q_chain, rows * 8);
-  if (!rc) rc = down(p_chain, P.p_chain, rows * 8);
-  if (!rc) rc = down(grad_chain, P.g_chain, rows * 8);
-  if (!rc) rc = down(logp_chain, P.logp_chain, lps * 8);
-  buf.release();
-  return rc;
 }
 
 }  // extern "C"
@@ -2444,20 +1926,6 @@ int exmc_hip_leapfrog_chain_normal_host(int device, int C, int d, const double* 
 // call alone: the flat order, a dense mass and resident chains stay as they were.
 // ------------------------------------------------------------------------------------------
 namespace {
-
-// one device allocation that lives for one call
-struct CallBuf {
-  void* p = nullptr;
-  ~CallBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
-    return EXMC_OK;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
 
 int ic_n_data(const exmc_hip_model* m) {
   switch (m->kind) {
@@ -2679,6 +2147,33 @@ int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, in
 #endif
 }
 
+// the _host forms: the caller's [C][S][d] trace staged in the device layout [S][d][C], `run(draws_dev,
+// out_dev)`, and its rows x N doubles back
+template <class Run>
+int ic_from_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains, int rows,
+                 double* out_host, Run&& run) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  const int N = ic_n_data(m);
+  if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
+  if (!draws_host || !out_host || d != m->d || n_draws < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
+    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  const int S = n_draws, C = n_chains;
+  std::vector<double> h((size_t)S * d * C);
+  for (int c = 0; c < C; c++)
+    for (int s = 0; s < S; s++)
+      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
+  CallBuf buf;
+  int rc = buf.alloc((h.size() + (size_t)rows * N) * 8);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  double* out = buf.as<double>() + h.size();
+  rc = run(buf.as<double>(), out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(out_host, out, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
+  return EXMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2700,27 +2195,9 @@ int exmc_hip_ic_stats(exmc_hip_model* m, const double* draws_dev, int n_draws, i
 
 int exmc_hip_ic_stats_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains,
                            double* stats_host) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-  const int N = ic_n_data(m);
-  if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
-  if (!draws_host || !stats_host || d != m->d || n_draws < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
-    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
-  HIP_TRY(hipSetDevice(m->device));
-  // [C][S][d] -> the device layout [S][d][C]
-  const int S = n_draws, C = n_chains;
-  std::vector<double> h((size_t)S * d * C);
-  for (int c = 0; c < C; c++)
-    for (int s = 0; s < S; s++)
-      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
-  CallBuf buf;
-  int rc = buf.alloc((h.size() + (size_t)4 * N) * 8);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-  double* stats = buf.as<double>() + h.size();
-  rc = ic_run(m, kIcStats, buf.as<double>(), S, d, C, stats);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(stats_host, stats, (size_t)4 * N * 8, hipMemcpyDeviceToHost));
-  return EXMC_OK;
+  return ic_from_host(m, draws_host, n_draws, d, n_chains, 4, stats_host, [&](const double* draws, double* stats) {
+    return ic_run(m, kIcStats, draws, n_draws, d, n_chains, stats);
+  });
 }
 
 int exmc_hip_ic_stats_from_ll(int device, const double* ll_dev, int n_draws, int n_data, int n_chains,
@@ -2758,27 +2235,9 @@ int exmc_hip_psis_stats(exmc_hip_model* m, const double* draws_dev, int n_draws,
 
 int exmc_hip_psis_stats_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains,
                              size_t scratch_bytes, double* out_host) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-  const int N = ic_n_data(m);
-  if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
-  if (!draws_host || !out_host || d != m->d || n_draws < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
-    return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
-  HIP_TRY(hipSetDevice(m->device));
-  // [C][S][d] -> the device layout [S][d][C]
-  const int S = n_draws, C = n_chains;
-  std::vector<double> h((size_t)S * d * C);
-  for (int c = 0; c < C; c++)
-    for (int s = 0; s < S; s++)
-      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
-  CallBuf buf;
-  int rc = buf.alloc((h.size() + (size_t)3 * N) * 8);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-  double* out = buf.as<double>() + h.size();
-  rc = exmc_hip_psis_stats(m, buf.as<double>(), S, d, C, scratch_bytes, out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(out_host, out, (size_t)3 * N * 8, hipMemcpyDeviceToHost));
-  return EXMC_OK;
+  return ic_from_host(m, draws_host, n_draws, d, n_chains, 3, out_host, [&](const double* draws, double* out) {
+    return exmc_hip_psis_stats(m, draws, n_draws, d, n_chains, scratch_bytes, out);
+  });
 }
 
 int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, int n_data, int n_chains,

@@ -4,7 +4,7 @@ signed_eps, mu, sigma)` -- one dispatch for K steps -- when the application has 
 `:fused_leapfrog_normal_meta = {mu, sigma}` (the model is d independent Normal(mu, sigma) coordinates) and
 d <= 256, and to `multi_step_fn` otherwise; both return `{all_q, all_p, all_logp, all_grad}`.
 
-Here the dispatch is one launch of `leapfrog_chain_normal_kernel` (exmc_amd/csrc/exmc_kernels.hpp) through
+Here the dispatch is one launch of `leapfrog_chain_normal_kernel` (exmc_amd/csrc/exmc_diag.hpp) through
 `exmc_hip_leapfrog_chain_normal_host`; f64 throughout (the reference's hook moves f32 binaries because its
 Vulkan device computes in f32, tree.ex:655-669). No CPU fallback.
 """

@@ -180,9 +180,11 @@ int exmc_hip_transitions_host(exmc_hip_model* m, double* q, double* logp, double
                               const double* inv_mass, int max_depth, int lanes,
                               exmc_hip_trace trace /* host, [C][n_draws][..] */);
 
-/* Shared warmup on chain 0 (sampler.ex:1053-1080 -> run_warmup :537-621): transitions run on
- * the GPU, dual averaging / Welford / window schedule on the host as the reference does
- * (step_size.ex, mass_matrix.ex are plain Erlang floats there too).
+/* Shared warmup on chain 0 (sampler.ex:1053-1080 -> run_warmup :537-621): the whole schedule
+ * runs in one kernel -- transitions, dual averaging (step_size.ex), Welford windows
+ * (mass_matrix.ex), the step-size searches; the host only lays out the windows.
+ * EXMC_HIP_HOST_WARMUP=1 keeps the adaptation scalars on the host instead (one launch per
+ * transition); both give the same bits.
  * init_q NULL => 0.1*normal_s per dim (sampler.ex:339-349). */
 int exmc_hip_warmup(exmc_hip_model* m, const double* init_q, exmc_hip_opts opts,
                     exmc_hip_tuning* tuning);

@@ -192,3 +192,52 @@ def test_plugin_build_form_is_part_of_the_cache_tag_and_missing_kernels_fail_the
     src.write_text(re.sub(r"const char\* b.*\n", "", src.read_text()))
     subprocess.check_call(["gcc", "-c", "-o", str(host2), str(src)])
     codegen._check_module_kernels(str(host2), [str(part)], common)     # every name defined: no error
+
+
+def test_library_built_from_two_units_defines_every_export():
+    """libexmc_hip.so is exmc_hip.hip linked with the model-free unit exmc_common.o: between them they
+    define the whole C ABI."""
+    from exmc_amd import _lib, build as _build
+    L = _lib.bind(_build.build())
+    for name in _lib.EXPORTS:
+        getattr(L, name)
+
+
+MODEL_FREE = ("exmc_hip_traj_create", "exmc_hip_build_full_tree_host", "exmc_hip_leapfrog_chain_normal_host",
+              "exmc_hip_last_error")
+
+
+def test_model_free_entry_points_are_defined_by_the_common_object_alone(tmp_path):
+    """A plug-in's main unit (exmc_hip.hip around the generated header) compiles none of the model-free
+    entry points again: exmc_common.o defines them, the main object only refers to them."""
+    from exmc_amd import build as _build
+    from exmc_amd import codegen
+    gen = codegen.generate(codegen.simple_ir())
+    codegen.build_plugin(gen)                                   # writes the generated header
+    main = str(tmp_path / "main.o")
+    subprocess.check_call(codegen.main_unit_cmd(codegen.plugin_paths(gen)[1], main), cwd=os.path.dirname(_build.SRC))
+
+    def defined(obj):
+        out = subprocess.run(["nm", "--defined-only", obj], capture_output=True, text=True, check=True).stdout
+        return set(ln.split()[-1] for ln in out.splitlines() if ln.split())
+    in_main, in_common = defined(main), defined(_build.build_common())
+    assert "exmc_hip_model_create" in in_main and "exmc_hip_model_create" not in in_common
+    for name in MODEL_FREE:
+        assert name in in_common and name not in in_main, name
+
+
+def test_one_last_error_string_per_library():
+    """exmc_hip_last_error returns the message of the call just made, whichever unit of the library
+    refused it, and a library never shows another's. Both calls fail their argument checks before any
+    device is touched."""
+    from exmc_amd import _lib, codegen
+    libs = [_lib.load(), _lib.bind(codegen.build_plugin(codegen.generate(codegen.simple_ir())))]
+    v = (C.c_double * 2)(0.0, 0.0)
+    for L in libs:
+        rc = L.exmc_hip_leapfrog_chain_normal_host(0, 1, 0, v, v, v, 1, 0.1, 0.0, 1.0, None, None, None, None)
+        assert rc == _lib.ERR_BADARG and L.exmc_hip_last_error().startswith(b"leapfrog_chain_normal:")   # the common unit
+        assert L.exmc_hip_model_create(0, 2, v, 2, 0, None) == _lib.ERR_BADARG
+        assert L.exmc_hip_last_error() == b"out is null"                                                 # the main unit
+    rc = libs[0].exmc_hip_leapfrog_chain_normal_host(0, 1, 0, v, v, v, 1, 0.1, 0.0, 1.0, None, None, None, None)
+    assert rc == _lib.ERR_BADARG and libs[0].exmc_hip_last_error().startswith(b"leapfrog_chain_normal:")
+    assert libs[1].exmc_hip_last_error() == b"out is null"
