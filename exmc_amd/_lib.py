@@ -38,6 +38,9 @@ COMPARE_EXPORTS = [
 # include/exmc_hip_psis.h (the end of exmc_hip_compare.h): PSIS-LOO with the Pareto k diagnostic
 PSIS_EXPORTS = ["exmc_hip_psis_stats", "exmc_hip_psis_stats_host", "exmc_hip_psis_stats_from_ll"]
 
+# include/exmc_hip_pointwise.h (the end of exmc_hip_compare.h): the per-datum terms of a block of datums
+POINTWISE_EXPORTS = ["exmc_hip_pointwise_loglik_range"]
+
 
 class ExmcHipError(RuntimeError):
     pass
@@ -146,6 +149,7 @@ def bind(path):
     L.exmc_hip_last_kernel_ms.restype = C.c_double
     L.exmc_hip_model_n_data.argtypes = [vp]
     L.exmc_hip_pointwise_loglik.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.exmc_hip_pointwise_loglik_range.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.exmc_hip_ic_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.exmc_hip_ic_stats_host.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, dp]
     L.exmc_hip_ic_stats_from_ll.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]

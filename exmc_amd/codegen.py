@@ -912,7 +912,11 @@ def _apply_ncp(ir, ncp):
     return nodes, info
 
 
-def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, waves_per_simd=1, scan=True):
+PW_GROUP = 16   # datums per generated function of the pointwise section (_emit_pointwise)
+
+
+def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, waves_per_simd=1, scan=True,
+             pointwise=False, _pw_group=PW_GROUP):
     """Compiler.compile_for_sampling (compiler.ex:46-58) as source text. `rewrite_passes` runs the
     reference's IR passes first (`rewrite`); without it the IR is taken as already rewritten
     (transforms explicit), which is what an exporter on the Elixir side sends. `lanes` = 16 / 32 /
@@ -926,7 +930,11 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
     is not restated here: an IR exported from a BEAM carries that order (`ir.term_order`, written by
     HipExport.to_json) and the terms follow it; an IR built in Python has no VM to ask and takes
     sorted-id order there too -- a reordering of the final sum (a few ulp of the log-density; the
-    gradient's entries are sums over the same terms)."""
+    gradient's entries are sums over the same terms).
+
+    `pointwise`: keep the per-datum terms of the obs nodes (`apply_obs_meta`: what a datum is) and emit
+    them as a section of their own (`_emit_pointwise`); everything before that section is the text
+    `pointwise=False` gives. `_pw_group`: datums per generated function; the results do not depend on it."""
     if rewrite_passes:
         ir = rewrite(ir)
     nodes, ncp_info = _apply_ncp(ir, ncp)
@@ -1051,8 +1059,21 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
             raise CodegenError("%r: an observation of a %r-transformed rv is not covered" % (id_, tr))
         return _apply_transform(g, tr, z), _log_abs_det_jacobian(g, tr, z)
 
-    def apply_obs_meta(elems, is_vec, meta, id_):
-        # compiler.ex:401-418: weight, mask, reduce
+    datums = []               # (name, node) of every datum, in term order then element index
+
+    def apply_obs_meta(elems, is_vec, meta, id_, pw=None):
+        # compiler.ex:401-418: weight, mask, reduce. pw: a list that takes the node's datums -- the
+        # kept elements (id, i) of a summed vector term after the weight (_obs_term says so: it is where
+        # the reduce is decided), else the one term as logp has it
+        t, per_element = _obs_term(elems, is_vec, meta, id_, pw)
+        if pw is not None and not per_element:
+            mk = meta.get("mask")
+            if is_vec or mk is None or bool(np.asarray(mk)):
+                pw.append((id_, t))
+        return t
+
+    def _obs_term(elems, is_vec, meta, id_, pw):
+        # -> the node's term, and whether its elements went to pw as datums of their own
         w = meta.get("weight")
         if w is not None:
             if is_vec:
@@ -1074,13 +1095,15 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
                 elems = [e if bool(mk[i]) else g.lit(0.0) for i, e in enumerate(elems)]
         red = meta.get("reduce")
         if not is_vec:
-            return elems
+            return elems, False
         if red == "sum":
-            return _sum_left(g, elems)            # Nx.sum on the BinaryBackend: left to right
+            if pw is not None:
+                pw.extend(((id_, i), e) for i, e in enumerate(elems) if mk is None or bool(mk[i]))
+            return _sum_left(g, elems), True      # Nx.sum on the BinaryBackend: left to right
         if red == "mean":
-            return g.div(_sum_left(g, elems), g.lit(float(len(elems))))
+            return g.div(_sum_left(g, elems), g.lit(float(len(elems)))), False
         if red == "logsumexp":
-            return _logsumexp(g, elems)
+            return _logsumexp(g, elems), False
         raise CodegenError("obs %r: a vector-valued term needs a reduce" % id_)
 
     terms = []
@@ -1161,7 +1184,7 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
             meta = dict(n.get("meta") or {})
             if vec and meta.get("reduce") is None:
                 meta["reduce"] = "sum"
-            terms.append(apply_obs_meta(t, vec, meta, id_))
+            terms.append(apply_obs_meta(t, vec, meta, id_))       # (no datums: constants of the data)
         else:
             tgt = nodes[n["target"]]
             if tgt["op"] != "rv":
@@ -1218,8 +1241,10 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
                     elems, is_vec = elementwise(tgt["dist"], x, params)
                     if tr is not None:
                         elems = [g.add(e, jac) for e in elems] if is_vec else g.add(elems, jac)
-            t = apply_obs_meta(elems, is_vec, meta, id_)
+            t = apply_obs_meta(elems, is_vec, meta, id_, datums if pointwise else None)
             terms.append(t)
+    if pointwise and not datums:
+        raise CodegenError("pointwise: the model has no datum (no obs node with a likelihood term)")
     total = terms[0]                              # sum_logps, compiler.ex:394-395
     for t in terms[1:]:
         total = g.add(t, total)
@@ -1277,6 +1302,17 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
         out.data = np.concatenate([out.data, out.lane_layout["data"]])
         out.lanes = lanes
     out.scan_chains = out.lane_layout["scan_chains"] if out.lane_layout is not None else []
+    out.datum_names, out.n_datums = None, -1
+    if pointwise:
+        # the per-datum terms as a section of their own; a model without a one-lane form ships the
+        # graph's data after the lane layout's table for it
+        doff = 0 if one_lane else int(out.data.size)
+        pw_data = np.zeros(0) if one_lane else np.asarray(g.data, dtype=np.float64)
+        out.header = "#ifndef EXMC_GEN_PW_SECTION\n" + out.header + \
+                     _emit_pointwise(g, datums, doff, int(pw_data.size), int(_pw_group))
+        out.data = np.concatenate([out.data, pw_data])
+        out.datum_names = [nm for nm, _ in datums]
+        out.n_datums = len(datums)
     out.digest = hashlib.sha256(out.header.encode()).hexdigest()[:16]
     out.n_ops = out.header.count("\n")
     return out
@@ -1413,6 +1449,80 @@ def _emit(g, total, grads, d):
     return "\n".join(L) + "\n"
 
 
+def _emit_pointwise(g, datums, doff, ndata, group):
+    """The pointwise section: the datum terms `datums` = [(name, node)] as straight-line text over the
+    graph, `group` datums per function, shared subexpressions once per function.
+      exmc_gen_pw_fold(data, c)   everything that depends on the data only, once per handle (host);
+                                  its data are data[EXMC_GEN_PW_DOFF ...]
+      exmc_gen_pw_eval(c, i0, i1, ...)   the datums [i0, i1) at one position: every function that meets
+                                  the range runs whole and only its stores are predicated, so a range of
+                                  one datum costs the arithmetic of its group (up to `group` datums) --
+                                  the price of sharing subexpressions inside a function
+    The includer says how a position entry is read (EXMC_GEN_PW_Q(j)), how datum i is written
+    (EXMC_GEN_PW_OUT(i, v), i0 and i1 in scope), what else the functions take (EXMC_GEN_PW_DECL /
+    EXMC_GEN_PW_PASS) and what a group function is (EXMC_GEN_PW_FN)."""
+    if group < 1:
+        raise CodegenError("pointwise: a generated function covers at least one datum")
+    leaf = ("lit", "data", "q")
+    slot, bodies = {}, []
+    for k0 in range(0, len(datums), group):
+        roots = [t for _, t in datums[k0:k0 + group]]
+        live = sorted(_reachable(roots, lambda i: () if g.const[i] or g.ops[i][0] in leaf else g.ops[i][1:]))
+        for i in live:
+            if g.const[i] and g.ops[i][0] != "lit" and i not in slot:
+                slot[i] = len(slot)
+        bodies.append((k0, roots, [i for i in live if not g.const[i] and g.ops[i][0] != "q"],
+                       sorted(g.ops[i][1] for i in live if g.ops[i][0] == "q")))
+    host = set(_reachable(slot, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data") else ()))
+
+    def ref(i, dyn):
+        op = g.ops[i]
+        if op[0] == "lit":
+            return _lit_text(op[1])
+        if dyn and i in slot:
+            return "c[%d]" % slot[i]
+        if op[0] == "data":
+            return "data[%d]" % op[1]
+        if op[0] == "q":
+            return "q%d" % op[1]
+        return "t%d" % i
+
+    def stmt(i, dyn):
+        return "  const double t%d = %s;" % (i, _expr_text(g.ops[i][0], [ref(x, dyn) for x in g.ops[i][1:]]))
+
+    L = ["#if !defined(EXMC_GEN_VEC_SECTION) && !defined(EXMC_GEN_LANES_SECTION)",
+         "/* per-datum log-likelihood terms (exmc_amd/codegen.py _emit_pointwise): %d datums in %d"
+         " function%s */" % (len(datums), len(bodies), "" if len(bodies) == 1 else "s"),
+         "#define EXMC_GEN_POINTWISE 1",
+         "#define EXMC_GEN_PW_N %d" % len(datums),
+         "#define EXMC_GEN_PW_NCONST %d" % max(1, len(slot)),
+         "#define EXMC_GEN_PW_DOFF %d   /* where the section's data start in data */" % doff,
+         "#define EXMC_GEN_PW_NDATA %d   /* ... and how many it ships itself (0: the one-lane form's) */" % ndata,
+         "#endif",
+         "#else   /* EXMC_GEN_PW_SECTION: the functions themselves, included once */",
+         "EXMC_GEN_HOST void exmc_gen_pw_fold(const double* data, double* c) {",
+         "  data += EXMC_GEN_PW_DOFF;"]
+    for i in sorted(host):
+        if g.ops[i][0] not in ("lit", "data"):
+            L.append(stmt(i, False))
+    for i, k in sorted(slot.items(), key=lambda kv: kv[1]):
+        L.append("  c[%d] = %s;" % (k, ref(i, False)))
+    if not slot:
+        L.append("  c[0] = 0.0;")
+    L += ["  (void)data;", "}", ""]
+    for n, (k0, roots, dyn, qs) in enumerate(bodies):
+        L.append("EXMC_GEN_PW_FN void exmc_gen_pw_%d(const double* c, int i0, int i1 EXMC_GEN_PW_DECL) {" % n)
+        L.extend("  const double q%d = EXMC_GEN_PW_Q(%d);" % (j, j) for j in qs)   # each entry read once
+        L.extend(stmt(i, True) for i in dyn)
+        L.extend("  EXMC_GEN_PW_OUT(%d, %s);" % (k0 + j, ref(t, True)) for j, t in enumerate(roots))
+        L += ["  (void)c; (void)i0; (void)i1;", "}", ""]
+    L.append("EXMC_GEN_FN void exmc_gen_pw_eval(const double* c, int i0, int i1 EXMC_GEN_PW_DECL) {")
+    for n, (k0, roots, _, _) in enumerate(bodies):
+        L.append("  if (i0 < %d && i1 > %d) exmc_gen_pw_%d(c, i0, i1 EXMC_GEN_PW_PASS);" % (k0 + len(roots), k0, n))
+    L += ["}", "#endif   /* EXMC_GEN_PW_SECTION */"]
+    return "\n".join(L) + "\n"
+
+
 # ---------------------------------------------------------------------------------------------
 # plug-in build + ModelSpec
 # ---------------------------------------------------------------------------------------------
@@ -1499,6 +1609,8 @@ def build_plugin(gen, force=False, verbose=False):
                 parts.append((6, 3))
             if 3 in layouts and "#define EXMC_GEN_WG 1" in gen.header:   # the workgroup form of the sampling kernel
                 parts.append((8, 3))
+            if "#define EXMC_GEN_POINTWISE 1" in gen.header:   # the per-datum terms over a trace (no layout of its own)
+                parts.append((9, 0))
             part_flags = ([f for f in flags if f != "-fPIC"] + ["--cuda-device-only"]) if modules else host_flags
             ext = "hsaco" if modules else "o"
             jobs += [([hipcc] + part_flags + defs + ["-DEXMC_PLUGIN_PART=%d" % k, "-DEXMC_PLUGIN_LAYOUT=%d" % lay, "-c", "-o",
@@ -1643,6 +1755,9 @@ class GeneratedSpec(ModelSpec):
         self.lib_path = lib_path
         self.vector_entries = dict(getattr(gen, "vector_entries", {}))   # id -> (offset, length)
         self.simplex_entries = dict(getattr(gen, "simplex_entries", {}))  # id -> (offset, K - 1)
+        # the datums of a model generated with pointwise=True (None / -1: it has no per-datum terms)
+        self.datum_names = None if getattr(gen, "datum_names", None) is None else list(gen.datum_names)
+        self.n_datums = getattr(gen, "n_datums", -1)
 
     def flat_order(self):
         # the generator lays the entries out in PointMap order already (ids sorted, a vector entry's
@@ -1699,11 +1814,11 @@ class GeneratedSpec(ModelSpec):
 
 
 def compile_ir(ir, ncp=True, name="generated", default_init=None, verbose=False, rewrite_passes=False,
-               lanes=None, waves_per_simd=1, scan=True):
+               lanes=None, waves_per_simd=1, scan=True, pointwise=False):
     """IR -> GeneratedSpec with its plug-in library built. Needs hipcc (no fallback). `lanes`,
-    `waves_per_simd`, `scan`: see `generate` / codegen_lanes.generate."""
+    `waves_per_simd`, `scan`, `pointwise`: see `generate` / codegen_lanes.generate."""
     gen = generate(ir, ncp=ncp, rewrite_passes=rewrite_passes, lanes=lanes, waves_per_simd=waves_per_simd,
-                   scan=scan)
+                   scan=scan, pointwise=pointwise)
     so = build_plugin(gen, verbose=verbose)
     return GeneratedSpec(gen, so, name=name, default_init=default_init)
 
@@ -1714,7 +1829,8 @@ def compile_ir(ir, ncp=True, name="generated", default_init=None, verbose=False,
 #                "params": {"mu": 0.0, "sigma": 5.0}, "transform": null}, ...,
 #                "y_obs": {"op": "obs", "target": "y", "value": [2.1, 1.8]}}}
 #   ("rewrite": true runs the reference's IR passes first; "scan": false keeps the random walks of
-#   the 64-lane layout unrolled (codegen_lanes.py, scan chains); obs nodes take reduce / weight / mask /
+#   the 64-lane layout unrolled (codegen_lanes.py, scan chains); "pointwise": true adds the per-datum
+#   terms (model.json then names the datums: datum_names, n_datums); obs nodes take reduce / weight / mask /
 #   censored / likelihood, {"op": "det", "fun": "affine", "args": [a, b, "x"]} and
 #   {"op": "meas_obs", "target": "x", "value": [...], "info": ["affine", a, b]} are accepted)
 #   out_dir gets exmc_gen_model.h, libexmc_hip_gen.so and model.json (d, var_names = the flat
@@ -1752,13 +1868,17 @@ def main(argv=None):
         raise SystemExit("usage: python -m exmc_amd.codegen model.json out_dir [--no-build]")
     doc = json.load(open(argv[0]))
     gen = generate(ir_from_json(doc), ncp=doc.get("ncp", True), rewrite_passes=doc.get("rewrite", False),
-                   lanes=doc.get("lanes"), waves_per_simd=doc.get("waves_per_simd", 1), scan=doc.get("scan", True))
+                   lanes=doc.get("lanes"), waves_per_simd=doc.get("waves_per_simd", 1), scan=doc.get("scan", True),
+                   pointwise=bool(doc.get("pointwise", False)))
     os.makedirs(argv[1], exist_ok=True)
     with open(os.path.join(argv[1], "exmc_gen_model.h"), "w") as f:
         f.write(gen.header)
     meta = dict(kind=CUSTOM, d=gen.d, var_names=gen.var_names, transforms=gen.transforms,
                 ncp_info=gen.ncp_info, data=gen.data.tolist(), digest=gen.digest, lanes_per_chain=gen.lanes,
                 scan=bool(doc.get("scan", True)), scan_chains=gen.scan_chains)
+    if gen.datum_names is not None:      # a vector obs's datum (id, i) is written [id, i]
+        meta.update(datum_names=[list(nm) if isinstance(nm, tuple) else nm for nm in gen.datum_names],
+                    n_datums=gen.n_datums)
     if "--no-build" not in argv:
         shutil.copyfile(build_plugin(gen), os.path.join(argv[1], "libexmc_hip_gen.so"))
         meta["library"] = "libexmc_hip_gen.so"

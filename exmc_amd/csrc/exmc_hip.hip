@@ -169,6 +169,7 @@ struct exmc_hip_model {
   RadonConsts rd{};
 #ifdef EXMC_CUSTOM_HEADER
   CustomConsts cu{};
+  const double* pw = nullptr;   // a model generated with per-datum terms: their folded constants in the image
 #endif
   DevBuf data;      // model data kept in HBM (logistic X,y; radon u,starts,floor,y)
   DevBuf zig;       // ki[256] u64, wi[256], fi[256]
@@ -1207,6 +1208,9 @@ int create_custom(exmc_hip_model* m, const double* data, int n_data, Names&) {
 #ifdef EXMC_GEN_LANES
   kGenData += EXMC_GEN_NLT;
 #endif
+#ifdef EXMC_GEN_POINTWISE
+  kGenData += EXMC_GEN_PW_NDATA;
+#endif
   if (n_data != kGenData || (n_data > 0 && !data)) return fail(EXMC_ERR_BADARG, "generated model: data length differs from the one it was generated for");
   m->d = EXMC_GEN_D;
 #ifdef EXMC_GEN_VEC
@@ -1232,8 +1236,17 @@ int create_custom(exmc_hip_model* m, const double* data, int n_data, Names&) {
 #ifdef EXMC_GEN_LANES
   folded.insert(folded.end(), data + EXMC_GEN_LOFF, data + EXMC_GEN_LOFF + EXMC_GEN_NLT);
 #endif
+#ifdef EXMC_GEN_POINTWISE
+  // the per-datum terms' own constants, after everything the sampling kernels read
+  const size_t pw_at = folded.size();
+  folded.resize(pw_at + EXMC_GEN_PW_NCONST);
+  exmc_gen_pw_fold(data, folded.data() + pw_at);
+#endif
   int rc = upload_image(m, folded);
   if (rc) return rc;
+#ifdef EXMC_GEN_POINTWISE
+  m->pw = m->data.as<double>() + pw_at;
+#endif
   m->cu.c = m->data.as<double>();
   m->cu.vc = m->data.as<double>() + EXMC_GEN_NCONST;
   m->cu.lt = m->data.as<double>() + n_folded;
@@ -1935,11 +1948,19 @@ int ic_n_data(const exmc_hip_model* m) {
     case EXMC_MODEL_SV_NCP: return 100;
     case EXMC_MODEL_LOGISTIC: return m->lg.N;
     case EXMC_MODEL_RADON: return (int)(m->rd.y - m->rd.fl);
+#ifdef EXMC_GEN_POINTWISE
+    case EXMC_MODEL_CUSTOM: return EXMC_GEN_PW_N;
+#endif
     default: return -1;
   }
 }
 
-enum IcMode { kIcStats, kIcMatrix, kIcPsis };   // [4][N] statistics, the matrix, PSIS-LOO's [3][N]
+// [4][N] statistics, the matrix, PSIS-LOO's [3][N], the matrix of a block of datums
+enum IcMode { kIcStats, kIcMatrix, kIcPsis, kIcRange };
+// the block of kIcRange
+struct IcRange {
+  int i0, nb;
+};
 
 struct IcGrid {
   long long chunk;
@@ -2073,29 +2094,73 @@ int ic_launch(exmc_hip_model* m, const Src& src, bool matrix, const double* draw
   return finish_timing(m);   // waits for the kernels: before `part` is freed
 }
 
+// the matrix ll[S][nb][C] of the datums r.i0 .. r.i0 + r.nb - 1: the launch psis_kind makes per block
+template <class Src>
+int ic_range(exmc_hip_model* m, const Src& src, const double* draws, int S, int C, IcRange r, double* out) {
+  const IcGrid g = ic_grid(S, C, r.nb);
+  const size_t lds = ic_lds_bytes(m->d);
+  if (lds > 64 * 1024) EXMC_KMAXLDS(pointwise_ll_range_kernel<Src>, lds);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  hipLaunchKernelGGL(pointwise_ll_range_kernel<Src>, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks), dim3(g.block),
+                     lds, m->stream, src, draws, S, m->d, C, r.i0, r.nb, g.chunk, out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);
+}
+
 // what ic_run does with the kind's source
 template <class Src>
 int ic_dispatch(exmc_hip_model* m, const Src& src, IcMode mode, size_t scratch_bytes, const double* draws, int S,
-                int C, int N, double* out) {
+                int C, int N, double* out, IcRange r) {
   if (mode == kIcPsis) return psis_kind(m, src, draws, S, C, N, scratch_bytes, out);
+  if (mode == kIcRange) return ic_range(m, src, draws, S, C, r, out);
   return ic_launch(m, src, mode == kIcMatrix, draws, S, C, N, out);
 }
 
 #endif
 
+#ifdef EXMC_GEN_POINTWISE
+// a generated model's per-datum terms (exmc_gen_pointwise.hpp): one lane per sample, the constants from
+// the handle's image
+int gen_pointwise(exmc_hip_model* m, const double* draws, int S, int C, IcRange r, double* out) {
+  GenPwParams P{m->pw, draws, out, S, C, r.i0, r.nb};
+  const long long n = (long long)S * C;
+  const long long blocks = (n + kGenPwBlock - 1) / kGenPwBlock;
+  if (blocks > 0x7FFFFFFFLL) return fail(EXMC_ERR_BADARG, "model comparison: too many samples for one launch");
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  EXMC_KLAUNCH(m->device, (gen_pointwise_kernel<EXMC_GEN_PW_N>), dim3((unsigned)blocks), dim3(kGenPwBlock), 0,
+               m->stream, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);
+}
+#endif
+
 // the kind's source of ll over a device trace; simple, eight_schools and sv keep their data in
 // the handle's constants, uploaded here for the call
 int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, int C, double* out,
-           size_t scratch_bytes = 0) {
+           size_t scratch_bytes = 0, IcRange r = IcRange{0, 0}) {
   if (check_model(m)) return EXMC_ERR_BADARG;
   const int N = ic_n_data(m);
   if (N < 0) return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
   if (!draws || !out || d != m->d || S < 1 || C < 1 || (long long)S * C < 2)
     return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
+  if (mode == kIcRange && (r.i0 < 0 || r.nb < 1 || r.i0 >= N || r.nb > N - r.i0))
+    return fail(EXMC_ERR_BADARG, "model comparison: the datum range is not inside [0, N)");
   HIP_TRY(hipSetDevice(m->device));
 #ifdef EXMC_ONLY_CUSTOM
-  (void)mode; (void)out; (void)scratch_bytes;
+  (void)scratch_bytes;
+#ifdef EXMC_GEN_POINTWISE
+  // the terms themselves; the reductions are libexmc_hip.so's (a plug-in carries no reduction kernels)
+  if (mode == kIcMatrix) return gen_pointwise(m, draws, S, C, IcRange{0, N}, out);
+  if (mode == kIcRange) return gen_pointwise(m, draws, S, C, r, out);
+  return fail(EXMC_ERR_UNSUPPORTED, "model comparison: a generated model reduces through "
+              "exmc_hip_pointwise_loglik_range and libexmc_hip.so's exmc_hip_ic_stats_from_ll / "
+              "exmc_hip_psis_stats_from_ll");
+#else
+  (void)mode; (void)out; (void)r;
   return fail(EXMC_ERR_UNSUPPORTED, "model comparison: this model kind has no per-datum terms");
+#endif
 #else
   if (mode == kIcPsis && (long long)S * C > kPsisMaxSamples)
     return fail(EXMC_ERR_BADARG, "psis: more than 2^31 - 1 pooled samples");
@@ -2117,10 +2182,10 @@ int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, in
   switch (m->kind) {
     case EXMC_MODEL_SIMPLE:
       rc = ic_dispatch(m, IcSimpleSrc{dimg.as<double>(), l2p, m->sp.tiny32}, mode, scratch_bytes, draws, S, C, N,
-                     out);
+                     out, r);
       break;
     case EXMC_MODEL_EIGHT_SCHOOLS:
-      rc = ic_dispatch(m, IcEightSchoolsSrc{dimg.as<double>(), l2p}, mode, scratch_bytes, draws, S, C, N, out);
+      rc = ic_dispatch(m, IcEightSchoolsSrc{dimg.as<double>(), l2p}, mode, scratch_bytes, draws, S, C, N, out, r);
       break;
     case EXMC_MODEL_SV:
     case EXMC_MODEL_SV_NCP: {
@@ -2131,16 +2196,16 @@ int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, in
       src.pi32 = m->sv.pi32;
       src.tiny32 = m->sv.tiny32;
       src.ncp = m->kind == EXMC_MODEL_SV_NCP;
-      rc = ic_dispatch(m, src, mode, scratch_bytes, draws, S, C, N, out);
+      rc = ic_dispatch(m, src, mode, scratch_bytes, draws, S, C, N, out, r);
       break;
     }
     case EXMC_MODEL_LOGISTIC:
       rc = ic_dispatch(m, IcLogisticSrc{m->lg.X, m->lg.y, m->lg.lo, m->lg.hi}, mode, scratch_bytes, draws, S, C, N,
-                     out);
+                     out, r);
       break;
     case EXMC_MODEL_RADON:
       rc = ic_dispatch(m, IcRadonSrc{m->rd.u, m->rd.cs, m->rd.fl, m->rd.y, m->rd.log2pi32, m->rd.tiny32}, mode, scratch_bytes,
-                     draws, S, C, N, out);
+                     draws, S, C, N, out, r);
       break;
   }
   return rc;
@@ -2186,6 +2251,11 @@ int exmc_hip_model_n_data(const exmc_hip_model* m) {
 int exmc_hip_pointwise_loglik(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
                               double* ll_dev) {
   return ic_run(m, kIcMatrix, draws_dev, n_draws, d, n_chains, ll_dev);
+}
+
+int exmc_hip_pointwise_loglik_range(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
+                                    int i0, int nb, double* ll_dev) {
+  return ic_run(m, kIcRange, draws_dev, n_draws, d, n_chains, ll_dev, 0, IcRange{i0, nb});
 }
 
 int exmc_hip_ic_stats(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,

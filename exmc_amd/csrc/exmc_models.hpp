@@ -1987,6 +1987,24 @@ __device__ __forceinline__ double genf_log1p(double x, bool& ok) {
 #endif
 #undef EXMC_GEN_LANES_SECTION
 #endif
+#ifdef EXMC_GEN_POINTWISE
+// the per-datum terms (exmc_amd/codegen.py _emit_pointwise; kernel: exmc_gen_pointwise.hpp): one lane
+// owns one sample of a trace [S][d][C]. qp = the sample's first position entry, entries qs doubles apart;
+// op = its datum i0 in the matrix, datums os doubles apart. A group of datums is a function of its own
+// (a call, like the transcendentals above): a vector obs of several hundred elements stays several
+// hundred short register allocations.
+#define EXMC_GEN_PW_SECTION
+#define EXMC_GEN_PW_FN static __host__ __device__ __noinline__
+#define EXMC_GEN_PW_DECL , const double* qp, size_t qs, double* op, size_t os
+#define EXMC_GEN_PW_PASS , qp, qs, op, os
+#define EXMC_GEN_PW_Q(j) qp[(size_t)(j) * qs]
+#define EXMC_GEN_PW_OUT(i, v)                                          \
+  do {                                                                 \
+    if ((i) >= i0 && (i) < i1) op[(size_t)((i) - i0) * os] = (v);     \
+  } while (0)
+#include EXMC_CUSTOM_HEADER
+#undef EXMC_GEN_PW_SECTION
+#endif
 
 
 namespace exmc {

@@ -63,6 +63,11 @@ EXMC_PK_DECL __global__ void nuts_kernel_wg<Custom<EXMC_GEN_LANES>, EXMC_GEN_LAN
     NutsParams, typename Custom<EXMC_GEN_LANES>::Consts);
 #endif
 #endif
+// part 9: the per-datum terms over a trace, when the header carries them (codegen.py generate(pointwise=True));
+// the kernel is no template on a layout
+#if defined(EXMC_GEN_POINTWISE) && (!defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 9)
+EXMC_PK_DECL __global__ void gen_pointwise_kernel<EXMC_GEN_PW_N>(GenPwParams);
+#endif
 #undef EXMC_PK_INDEP
 #undef EXMC_PK_NUTS
 #undef EXMC_PK_WARM

@@ -12,8 +12,14 @@ The unit is the datum of a built-in kind (include/exmc_hip_compare.h, DESIGN.md 
 one y_i, one return r_t. `draws` is the device trace [S][d][C] or a host array [C][S][d], as for
 exmc_amd/diagnostics.py. The per-datum statistics (lppd_i, p_waic_i, elpd_loo_i, p_loo_i) are formed on
 the GPU in one pass over the trace; the totals and `se` here, with the reference's formulas, summing in
-datum order. Models without a kind (generated plug-ins) form their ll matrix themselves and use the
-*_from_pointwise forms. No CPU fallback.
+datum order.
+
+A generated model takes part when it was compiled with its per-datum terms (codegen.compile_ir(...,
+pointwise=True)): its datums are the terms of its obs nodes (DESIGN.md "Per-datum terms of generated
+models"). Its plug-in evaluates them over the trace a block of datums at a time
+(exmc_hip_pointwise_loglik_range) and libexmc_hip.so's model-free reductions take each block; the
+result per datum does not depend on the blocking. Generated models compiled without them form their ll
+matrix themselves and use the *_from_pointwise forms. No CPU fallback.
 """
 import math
 
@@ -21,10 +27,16 @@ import numpy as np
 
 from . import _lib
 from .diagnostics import _device_trace, _ordered_after_torch
+from .codegen import CUSTOM   # a generated model's plug-in
 from .models import EIGHT_SCHOOLS, LOGISTIC, RADON, SIMPLE, SV, SV_NCP
 
 # pointwise_log_likelihood refuses matrices above this many bytes: waic / loo never form them
 POINTWISE_MAX_BYTES = 2 << 30
+# waic / loo of a generated model: the scratch matrix of a block of datums (scratch_bytes=0)
+GENERATED_DEFAULT_SCRATCH = 1 << 30
+# psis_loo of a generated model with scratch_bytes=0: EXMC_PSIS_DEFAULT_SCRATCH of include/exmc_hip_psis.h
+# (tests/test_codegen_pointwise.py holds the two together)
+PSIS_DEFAULT_SCRATCH = 8 << 30
 
 
 def n_data(compiled):
@@ -48,6 +60,12 @@ def datum_names(compiled):
     every index is 0-based, as the reference's {obs_id, idx} keys are"""
     N = n_data(compiled)
     kind = compiled.spec.kind
+    if kind == CUSTOM:
+        names = getattr(compiled.spec, "datum_names", None)
+        if names is None or len(names) != N:
+            raise _lib.ExmcHipError("model comparison: the plug-in of %s reports %d datums, its spec names %s"
+                                    % (compiled.spec.name, N, "none" if names is None else len(names)))
+        return list(names)
     if kind == EIGHT_SCHOOLS:
         return ["y_obs_%d" % j for j in range(N)]
     if kind == SIMPLE:
@@ -88,13 +106,41 @@ def pointwise_log_likelihood(compiled, draws, max_bytes=POINTWISE_MAX_BYTES):
     return ll, [names[k] for k in order]
 
 
-def pointwise_stats(compiled, draws):
-    """the per-datum statistics [4][N] (lppd, p_waic, elpd_loo, p_loo) in the CALLER's datum order"""
+def _generated_blocks(compiled, x, N, scratch_bytes, rows, reduce_block):
+    """A generated model's datums in blocks of Nb = scratch_bytes / (8 S C), one at the least: the plug-in
+    writes the block's matrix ll[S][nb][C] into scratch, reduce_block(main library, ll pointer, nb, out
+    pointer) -- a *_from_ll entry point of libexmc_hip.so -- reduces it, its rows go to their columns."""
+    import torch
+    S, d, C = x.shape
+    Nb = max(1, min(N, int(scratch_bytes) // (8 * S * C)))
+    ll = torch.empty((S, Nb, C), dtype=torch.float64, device=x.device)
+    blk = torch.empty((rows, Nb), dtype=torch.float64, device=x.device)
+    out = np.empty((rows, N))
+    main = _lib.load()
+    _ordered_after_torch(x)
+    for i0 in range(0, N, Nb):
+        nb = min(Nb, N - i0)
+        # (both calls return when their results are written: the scratch is free for the next block)
+        compiled.check(compiled.L.exmc_hip_pointwise_loglik_range(compiled.h, x.data_ptr(), S, d, C, i0, nb,
+                                                                  ll.data_ptr()))
+        _lib.check(reduce_block(main, ll.data_ptr(), nb, blk.data_ptr()), main)
+        out[:, i0:i0 + nb] = blk.cpu().numpy().reshape(-1)[:rows * nb].reshape(rows, nb)
+    return out
+
+
+def pointwise_stats(compiled, draws, scratch_bytes=0):
+    """the per-datum statistics [4][N] (lppd, p_waic, elpd_loo, p_loo) in the CALLER's datum order.
+    scratch_bytes: a generated model's block matrix (0: GENERATED_DEFAULT_SCRATCH); kinds reduce in one
+    pass and take no scratch."""
     import torch
     N = n_data(compiled)
     x = _device_trace(compiled, draws)
     S, d, C = x.shape
     _check_samples(S, C)
+    if compiled.spec.kind == CUSTOM:
+        dev = x.device.index
+        return _generated_blocks(compiled, x, N, scratch_bytes or GENERATED_DEFAULT_SCRATCH, 4,
+                                 lambda L, ll, nb, out: L.exmc_hip_ic_stats_from_ll(dev, ll, S, nb, C, out))
     out = torch.empty((4, N), dtype=torch.float64, device=x.device)
     _ordered_after_torch(x)
     compiled.check(compiled.L.exmc_hip_ic_stats(compiled.h, x.data_ptr(), S, d, C, out.data_ptr()))
@@ -141,6 +187,11 @@ def psis_pointwise_stats(compiled, draws, scratch_bytes=0):
     x = _device_trace(compiled, draws)
     S, d, C = x.shape
     _check_samples(S, C)
+    if compiled.spec.kind == CUSTOM:
+        dev = x.device.index
+        st = _generated_blocks(compiled, x, N, scratch_bytes or PSIS_DEFAULT_SCRATCH, 3,
+                               lambda L, ll, nb, out: L.exmc_hip_psis_stats_from_ll(dev, ll, S, nb, C, out))
+        return st, S * C
     out = torch.empty((3, N), dtype=torch.float64, device=x.device)
     _ordered_after_torch(x)
     compiled.check(compiled.L.exmc_hip_psis_stats(compiled.h, x.data_ptr(), S, d, C, scratch_bytes, out.data_ptr()))
@@ -217,14 +268,15 @@ def _loo_result(st, names):
     return r
 
 
-def waic(compiled, draws):
-    """waic/1 over the model's datums; "pointwise" holds the per-datum arrays in the caller's order"""
-    return _waic_result(pointwise_stats(compiled, draws), datum_names(compiled))
+def waic(compiled, draws, scratch_bytes=0):
+    """waic/1 over the model's datums; "pointwise" holds the per-datum arrays in the caller's order.
+    scratch_bytes: see pointwise_stats (generated models only)"""
+    return _waic_result(pointwise_stats(compiled, draws, scratch_bytes), datum_names(compiled))
 
 
-def loo(compiled, draws):
+def loo(compiled, draws, scratch_bytes=0):
     """loo/1 (plain importance-sampling LOO, loo_i_basic) over the model's datums"""
-    return _loo_result(pointwise_stats(compiled, draws), datum_names(compiled))
+    return _loo_result(pointwise_stats(compiled, draws, scratch_bytes), datum_names(compiled))
 
 
 def waic_from_pointwise(ll, names=None, device=None):

@@ -10,8 +10,10 @@
  *   elpd_loo_i = -log_mean_exp(-ll_i) (plain importance-sampling LOO, loo_i_basic), p_loo_i =
  *   lppd_i - elpd_loo_i; accumulated over fixed chunks of samples in a fixed order and merged
  *   left to right, so the bits depend on (S, C) and the trace only.
- * EXMC_MODEL_STD_NORMAL (no data) and generated models (EXMC_MODEL_CUSTOM) answer
- * EXMC_ERR_UNSUPPORTED: form their ll on the host and use exmc_hip_ic_stats_from_ll.
+ * EXMC_MODEL_STD_NORMAL (no data) and generated models (EXMC_MODEL_CUSTOM) built without per-datum
+ * terms answer EXMC_ERR_UNSUPPORTED: form their ll on the host and use exmc_hip_ic_stats_from_ll. A
+ * model generated WITH them (exmc_hip_pointwise.h) answers exmc_hip_model_n_data and the two matrix
+ * calls; its reductions are exmc_hip_pointwise_loglik_range and libexmc_hip.so's *_from_ll.
  * Errors: EXMC_ERR_BADARG for a null pointer, d != the model's dimension, n_draws < 1,
  * n_chains < 1 or fewer than 2 samples in all (the variance needs n >= 2).
  *
@@ -59,5 +61,7 @@ int exmc_hip_ic_stats_from_ll(int device, const double* ll_dev, int n_draws, int
 
 /* PSIS-LOO with the Pareto k diagnostic: the exmc_hip_psis_* entry points, part of this interface */
 #include "exmc_hip_psis.h"
+/* the per-datum terms of a block of datums: what generated models take part through */
+#include "exmc_hip_pointwise.h"
 
 #endif
