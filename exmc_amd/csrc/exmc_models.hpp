@@ -81,6 +81,14 @@ struct ModelDefaults {
   static constexpr int kWgImageDoubles = 0;   // the image's size; wg_stage fills it, wg_attach points a lane at it
   template <class C>
   __host__ __device__ static bool wg_ok(const C&) { return false; }
+  // the one-wave sampling form walks the tree a leaf pair per pass, the pair merged in registers
+  // (exmc_nuts.hpp leaf_pair): for models whose pass is mostly tree bookkeeping. Switched on per
+  // model where measured to gain. kLeafPairExp: the pair's three exponentials as one lane-batched
+  // evaluation. kLeanMomentum: the momentum draw's stepping loop carries only the tail word of each
+  // lane's generator state (exmc_nuts.hpp draw_momentum_variates)
+  static constexpr bool kLeafPairs = false;
+  static constexpr bool kLeafPairExp = false;
+  static constexpr bool kLeanMomentum = false;
 };
 
 // the dynamic LDS of the running kernel (every extern __shared__ array names the same base)
@@ -122,6 +130,13 @@ struct EightSchools : ModelDefaults {
 #define EXMC_ES_PIPE_LEVELS 2
 #endif
   static constexpr int kPipeNutsLevels = (G == 16) ? EXMC_ES_PIPE_LEVELS : 0;
+  // bit 0 kLeafPairs, bit 1 kLeafPairExp, bit 2 kLeanMomentum (to measure each alone)
+#ifndef EXMC_ES_LEAF_PAIRS
+#define EXMC_ES_LEAF_PAIRS 7
+#endif
+  static constexpr bool kLeafPairs = (G == 16) && (EXMC_ES_LEAF_PAIRS & 1);
+  static constexpr bool kLeafPairExp = (G == 16) && (EXMC_ES_LEAF_PAIRS & 2);
+  static constexpr bool kLeanMomentum = (G == 16) && (EXMC_ES_LEAF_PAIRS & 4);
   using MM = Math<kVregMath>;
   using Consts = EightSchoolsConsts;
   struct Lane {

@@ -41,6 +41,7 @@
 
 // EXMC_ABLATE = 1..4 builds timing-only variants (U-turn reductions / merge transcendentals /
 // model gradient / leaf exp stubbed out) for tools/kernel_probe.py; outputs are wrong then.
+// They walk the tree a leaf per pass whatever M::kLeafPairs says (nuts_run).
 #ifndef EXMC_ABLATE
 #define EXMC_ABLATE 0
 #endif
@@ -588,6 +589,95 @@ __device__ __forceinline__ void draw_momentum_orbit(const NutsLane<M, G>& L, Rng
   }
 }
 
+// draw_momentum_variates below for the identity order (L.perm == nullptr) and G < 64, with less per
+// step (M::kLeanMomentum). normal_fast reads only the tail word of the state in front of a draw, so
+// a lane keeps that word alone; the head word of state i is the tail word of state i - 1 (see the
+// orbit form above) and is fetched from the lane of dimension i - 1 -- or, for the first draw of a
+// pass, taken from the state the pass started at -- only when draw i goes the long way. The first
+// pass starts at draw 0 in every group, so its steps need no `act` selects.
+template <class M, int G>
+__device__ __forceinline__ void draw_momentum_lean(const NutsLane<M, G>& L, Rng& rng,
+                                                   double (&z)[M::DPL]) {
+  constexpr int D = M::D, DPL = M::DPL;
+  static_assert(G < 64, "the 64-lane layouts have the orbit form");
+  const int base = (threadIdx.x & 63) & ~(G - 1);
+#pragma unroll
+  for (int k = 0; k < DPL; k++) z[k] = 0.0;
+  int pos = 0;   // draws [0, pos) are final and rng stands in front of draw pos
+  bool first = true;   // wave-uniform
+  for (;;) {
+    Rng r2 = rng;
+    uint64_t sb[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) sb[k] = 0;
+    // kept rolled, as in draw_momentum_variates
+    if (first) {
+#pragma nounroll
+      for (int i = 0; i < D; i++) {
+#pragma unroll
+        for (int k = 0; k < DPL; k++) sb[k] = (L.rank[k] == i) ? r2.b : sb[k];
+        rng_advance(r2);
+      }
+    } else {
+      const int i0 = wave_min_pos<G>(pos);
+#pragma nounroll
+      for (int i = i0; i < D; i++) {
+        const bool act = i >= pos;
+#pragma unroll
+        for (int k = 0; k < DPL; k++) sb[k] = (act && (L.rank[k] == i)) ? r2.b : sb[k];
+        Rng nx = r2;
+        rng_advance(nx);
+        r2.a = act ? nx.a : r2.a;
+        r2.b = act ? nx.b : r2.b;
+      }
+    }
+    first = false;
+    bool fail[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      const bool live = L.valid[k] && (L.rank[k] >= pos);
+      double zz;
+      const bool acc = normal_fast(rng_scramble(sb[k]), L.zt, zz);
+      fail[k] = live && !acc;
+      z[k] = (live && acc) ? zz : z[k];
+    }
+    int j = D;   // first draw of this group that needs the long way, D if none
+#pragma unroll
+    for (int k = DPL - 1; k >= 0; k--) {
+      const unsigned long long m = __ballot(fail[k] ? 1 : 0);
+      const unsigned long long gm = (m >> base) & ((1ULL << G) - 1ULL);
+      j = (gm != 0) ? (k * G + __ffsll((long long)gm) - 1) : j;
+    }
+    if (__any((j < D) ? 1 : 0) == 0) {
+      rng = r2;
+      break;
+    }
+    if (j < D) {
+      // state j = (tail word of state j - 1, tail word of state j); j - 1 >= pos was stepped over
+      // in this pass, so the lane of dimension j - 1 holds its tail word
+      const int jp = (j > pos) ? j - 1 : j;
+      uint64_t bj = 0, bp = 0;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) {
+        bj = (k == j / G) ? sb[k] : bj;
+        bp = (k == jp / G) ? sb[k] : bp;
+      }
+      Rng rj;
+      rj.b = __shfl(bj, base | (j & (G - 1)), 64);
+      const uint64_t hp = __shfl(bp, base | (jp & (G - 1)), 64);
+      rj.a = (j > pos) ? hp : rng.a;
+      const double zz = rng_normal(rj, L.zt, L.nor_r);
+#pragma unroll
+      for (int k = 0; k < DPL; k++) z[k] = (L.rank[k] == j) ? zz : z[k];
+      rng = rj;
+      pos = j + 1;
+    } else {
+      rng = r2;
+      pos = D;
+    }
+  }
+}
+
 template <class M, int G>
 __device__ __forceinline__ void draw_momentum_variates(const NutsLane<M, G>& L, Rng& rng,
                                                        double (&z)[M::DPL]) {
@@ -595,6 +685,12 @@ __device__ __forceinline__ void draw_momentum_variates(const NutsLane<M, G>& L, 
   if constexpr (G == 64 && M::kRngOrbit && D + EXMC_RNG_ORBIT_MARGIN <= 128) {
     draw_momentum_orbit<M, G>(L, rng, z);
     return;
+  }
+  if constexpr (G < 64 && M::kLeanMomentum) {
+    if (L.perm == nullptr) {
+      draw_momentum_lean<M, G>(L, rng, z);
+      return;
+    }
   }
   const int base = (threadIdx.x & 63) & ~(G - 1);
 #pragma unroll
@@ -737,6 +833,12 @@ __device__ __forceinline__ void draw_momentum(const NutsLane<M, G>& L, Rng& rng,
 // ------------------------------------------------------------------------------------------
 struct NoPipe {
   static constexpr bool kOn = false;
+  static constexpr bool kLeafPairs = true;   // nuts_run may walk leaf pairs itself (M::kLeafPairs)
+};
+// one wave, a pass per leaf whatever the model's traits say
+struct NoPipeLeaf {
+  static constexpr bool kOn = false;
+  static constexpr bool kLeafPairs = false;
 };
 
 // a finished subtree as the tree wave continues with it (nuts_run's c_* variables)
@@ -759,6 +861,7 @@ struct PipeLeaf {
 template <int DPL>
 struct PipeBox {
   static constexpr bool kOn = true;
+  static constexpr bool kLeafPairs = false;
   static constexpr int kQuit = 4 * DPL + 4;   // start row: the tree wave abandons the kernel
   static constexpr int kCtrl = 4 * DPL + 5;
   static constexpr int kSlot = kCtrl + 4;
@@ -860,11 +963,17 @@ __host__ __device__ constexpr size_t pipe_lds_doubles() { return (size_t)PipeBox
 // a diverged first leaf of a pair), or (a, b) merged at level 0 exactly as nuts_run's own ascent
 // does at lvl 0 (tree.ex:1390-1476). q0 / g0: the state leaf a started from (a diverged leaf's
 // proposal, tree.ex:1042-1048). The proposal draw comes from trng only when the pair is merged.
-template <class M, int G>
+// lse(a.lsw, b.lsw): the pair's log_sum_exp, for a caller that already holds it (leaf_pair).
+struct PairLse {
+  template <class MM>
+  __device__ __forceinline__ double operator()(MM, double a, double b) const { return MM::log_sum_exp(a, b); }
+};
+
+template <class M, int G, class Lse = PairLse>
 __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const PipeLeaf<M::DPL>& a,
                                                const PipeLeaf<M::DPL>& b, bool pair,
                                                const double (&q0)[M::DPL], const double (&g0)[M::DPL],
-                                               Rng& trng, PipeUnit<M::DPL>& u) {
+                                               Rng& trng, PipeUnit<M::DPL>& u, Lse&& lse = Lse{}) {
   constexpr int DPL = M::DPL;
   using MM = Math<M::kVregMath>;
 #pragma unroll
@@ -881,7 +990,7 @@ __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const Pi
   u.div = a.div;
   u.turn = false;
   if (pair && !a.div) {
-    const double lsw = MM::log_sum_exp(a.lsw, b.lsw);
+    const double lsw = lse(MM{}, a.lsw, b.lsw);
     const double uu = rng_uniform(trng);
     const bool use_b = uu < MM::exp_le0(b.lsw - lsw);   // lsw >= b.lsw
     bool turning = b.div;
@@ -912,6 +1021,66 @@ __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const Pi
     u.div = b.div;
     u.turn = turning;
   }
+}
+
+// The one-wave form of a unit (M::kLeafPairs): one leapfrog from (q, p, g) in place, or two when
+// `pair` (wave-uniform), and the leaves' scalars as nuts_run's leaf block computes them. q0 / g0:
+// the state the first leapfrog started from. With both leaves in hand the three exponentials of
+// the pair -- the two accept statistics and the one inside log_sum_exp(a.lsw, b.lsw) -- have
+// independent, group-uniform arguments: one evaluation with each argument on a lane of its own
+// (lane_batch; M::kLeafPairExp), the same function on the same bits. lsw_ab is that log_sum_exp,
+// for pipe_pair_unit.
+template <class M, int G>
+__device__ __forceinline__ void leaf_pair(const typename M::Consts& mc, const NutsLane<M, G>& L,
+                                          double eps_dir, double jlp0, bool pair,
+                                          double (&q)[M::DPL], double (&p)[M::DPL], double (&g)[M::DPL],
+                                          double (&q0)[M::DPL], double (&g0)[M::DPL],
+                                          PipeLeaf<M::DPL>& a, PipeLeaf<M::DPL>& b, double& lsw_ab) {
+  constexpr int DPL = M::DPL;
+  using MM = Math<M::kVregMath>;
+  // batched_leapfrog.ex:79-85 and tree.ex:1042-1048 without a branch (see pipe_integrate_transition)
+  auto leap = [&](PipeLeaf<DPL>& f) -> double {
+    const double h = eps_dir / 2.0;
+#pragma unroll
+    for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
+    mass_drift<M, G>(L, eps_dir, p, q);
+    f.logp = M::logp_grad(mc, L.ln, L.l, q, g);
+#pragma unroll
+    for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
+    const double jlp = f.logp - mass_ke<M, G>(L, p);
+    const bool fin = exmc_isfinite(jlp);
+    const double dl = jlp - jlp0;
+    f.div = fin ? (dl < -1000.0) : true;
+    f.lsw = fin ? dl : -1001.0;
+#pragma unroll
+    for (int k = 0; k < DPL; k++) { f.q[k] = q[k]; f.p[k] = p[k]; f.g[k] = g[k]; }
+    return fmin(dl, 0.0);
+  };
+#pragma unroll
+  for (int k = 0; k < DPL; k++) { q0[k] = q[k]; g0[k] = g[k]; }
+  double x[3];
+  x[0] = leap(a);
+  lsw_ab = 0.0;
+  if (!pair) {
+    a.acc = a.div ? 0.0 : fmin(1.0, MM::exp_le0(x[0]));
+    b = a;
+    return;
+  }
+  x[1] = leap(b);
+  // log_sum_exp(a.lsw, b.lsw) with its exponential taken out (Math::log_sum_exp)
+  const double mx = (a.lsw > b.lsw) ? a.lsw : b.lsw;
+  const double mn = (a.lsw > b.lsw) ? b.lsw : a.lsw;
+  x[2] = mn - mx;
+  if constexpr (M::kLeafPairExp && G >= 3) {
+    lane_batch<G>(x, L.l, [](double v) { return MM::exp_le0(v); });
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) x[i] = MM::exp_le0(x[i]);
+  }
+  a.acc = a.div ? 0.0 : fmin(1.0, x[0]);
+  b.acc = b.div ? 0.0 : fmin(1.0, x[1]);
+  const bool none = (mx == -exmc_from_bits(EXMC_INF_BITS) || mx == -1.0e300);
+  lsw_ab = none ? -1.0e300 : mx + MM::log_ge1(1.0 + x[2]);
 }
 
 // the integrator wave's side of one transition (mirror of nuts_run's skeleton)
@@ -1144,11 +1313,17 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
       }
       EXMC_PROF(1)
 
-      // one-wave form: a pass per leaf, ascent from level 0. Pipelined form: a pass per unit of the
-      // integrator wave (a leaf in doubling 0, afterwards a leaf pair merged at level 0), so loop
-      // level lvl is tree level lvl + kLvl0
-      constexpr int kLvl0 = Pipe::kOn ? 1 : 0;
-      const int nlev = (Pipe::kOn && depth > 0) ? depth - 1 : depth;
+      // one-wave form: a pass per leaf, ascent from level 0. Pipelined form, and the one-wave form
+      // of a model with kLeafPairs: a pass per unit (a leaf in doubling 0, afterwards a leaf pair
+      // merged at level 0 in registers: the integrator wave's, or leaf_pair's), so loop level lvl is
+      // tree level lvl + kLvl0: no level-0 node is ever parked, tree level 1 lives in stack slot 0 and
+      // the topmost slot of the leaf-per-pass form goes unused. The timing-only EXMC_ABLATE builds keep
+      // the leaf-per-pass walk, where all four of their modes apply.
+      static_assert(!M::kLeafPairExp || M::kLeafPairs, "kLeafPairExp batches the exponentials of kLeafPairs' pair");
+      constexpr bool kOwnPairs = M::kLeafPairs && Pipe::kLeafPairs && EXMC_ABLATE == 0;
+      constexpr bool kUnits = Pipe::kOn || kOwnPairs;
+      constexpr int kLvl0 = kUnits ? 1 : 0;
+      const int nlev = (kUnits && depth > 0) ? depth - 1 : depth;
       const int nleaf = 1 << nlev;
       for (int leaf = 0; leaf < nleaf; leaf++) {
         if constexpr (M::kNutsWavesPerSimd == 2 && !Pipe::kOn) {
@@ -1172,7 +1347,12 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
         if (leaf > 0 && __any(alive ? 1 : 0) == 0) break;
         EXMC_PROF_COUNT(9)
         double logp_new = 0.0, jlp = 0.0;
-        if constexpr (!Pipe::kOn) {
+        PipeLeaf<DPL> la, lb;
+        double lsw_ab = 0.0;
+        if constexpr (kOwnPairs) {
+          // ---- the unit's leapfrogs on every lane, as below ----
+          leaf_pair<M, G>(mc, L, eps_dir, jlp0, depth > 0, q, p, g, qold, gold, la, lb, lsw_ab);
+        } else if constexpr (!Pipe::kOn) {
           // ---- one leapfrog on every lane (batched_leapfrog.ex:79-85); idle groups integrate
           // scratch registers so that wave-cooperative models see all 64 lanes ----
           const double h = eps_dir / 2.0;
@@ -1202,15 +1382,17 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
           bool c_div, c_turn = false;
           double c_lsw, c_acc, c_logpP;
           int c_n = 1;
-          if constexpr (Pipe::kOn) {
-            // the integrator wave computed this unit while the previous one was merged here
+          if constexpr (kUnits) {
             PipeUnit<DPL> pu;
-            {
-              PipeLeaf<DPL> la, lb;
+            if constexpr (Pipe::kOn) {
+              // the integrator wave computed this unit while the previous one was merged here
               pipe->get_leaf(0, la);
               if (depth > 0) pipe->get_leaf(1, lb);
               else lb = la;
               pipe_pair_unit<M, G>(L, la, lb, depth > 0, q, g, trng, pu);
+            } else {
+              pipe_pair_unit<M, G>(L, la, lb, depth > 0, qold, gold, trng, pu,
+                                   [&](auto, double, double) { return lsw_ab; });
             }
 #pragma unroll
             for (int k = 0; k < DPL; k++) {
@@ -2346,7 +2528,7 @@ __global__ void __launch_bounds__(kPipe ? 2 * kNutsBlock : kNutsBlock)
       const int cap = (in_window && i < 200) ? (P.max_depth < 8 ? P.max_depth : 8) : P.max_depth;
       auto idle = [&]() { da.prepare(); };
       if constexpr (kPipe) nuts_run<M, G, LDSL>(mc, L, st, 1, exmc_exp(da.log_epsilon), cap, sink, &pipe, idle);
-      else nuts_run<M, G, LDSL>(mc, L, st, 1, exmc_exp(da.log_epsilon), cap, sink, (NoPipe*)nullptr, idle);
+      else nuts_run<M, G, LDSL>(mc, L, st, 1, exmc_exp(da.log_epsilon), cap, sink, (NoPipeLeaf*)nullptr, idle);
       divergences += diverged ? 1 : 0;
       da.update(accept);
       if (in_window) {
