@@ -41,6 +41,10 @@ PSIS_EXPORTS = ["exmc_hip_psis_stats", "exmc_hip_psis_stats_host", "exmc_hip_psi
 # include/exmc_hip_pointwise.h (the end of exmc_hip_compare.h): the per-datum terms of a block of datums
 POINTWISE_EXPORTS = ["exmc_hip_pointwise_loglik_range"]
 
+# include/exmc_hip_pathfinder.h: Exmc.Pathfinder, one L-BFGS path per lane group
+PATHFINDER_EXPORTS = ["exmc_hip_pathfinder", "exmc_hip_pathfinder_host"]
+PF_MAX_HISTORY = 6
+
 
 class ExmcHipError(RuntimeError):
     pass
@@ -54,6 +58,11 @@ class Opts(C.Structure):
 class Tuning(C.Structure):
     _fields_ = [("epsilon", C.c_double), ("inv_mass", C.c_double * MAX_D),
                 ("warmup_divergences", C.c_int)]
+
+
+class PfOpts(C.Structure):
+    _fields_ = [("num_draws", C.c_int), ("max_iters", C.c_int), ("history_size", C.c_int),
+                ("seed", C.c_uint64), ("lanes_per_chain", C.c_int)]
 
 
 class Trace(C.Structure):
@@ -156,6 +165,8 @@ def bind(path):
     L.exmc_hip_psis_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
     L.exmc_hip_psis_stats_host.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_size_t, dp]
     L.exmc_hip_psis_stats_from_ll.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.exmc_hip_pathfinder.argtypes = [vp, PfOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.exmc_hip_pathfinder_host.argtypes = [vp, PfOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip, ip]
     _libs[path] = L
     return L
 

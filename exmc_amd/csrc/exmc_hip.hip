@@ -9,6 +9,7 @@
 // is no CPU fallback: without a HIP device every compute entry point returns EXMC_ERR_NO_DEVICE.
 #include "../../include/exmc_hip.h"
 #include "../../include/exmc_hip_compare.h"
+#include "../../include/exmc_hip_pathfinder.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1373,11 +1374,15 @@ int exmc_hip_logp_grad_host(exmc_hip_model* m, const double* q, int C, int lanes
   rc = dispatch(m, lanes, [&](auto tag, const auto& mc) {
     using T = decltype(tag);
     const size_t xlds = aux_lds_bytes<typename T::M>();
+    HIP_TRY(hipEventRecord(m->ev0, m->stream));   // exmc_hip_last_kernel_ms: this launch alone
     EXMC_KLAUNCH(m->device, (logp_grad_kernel<typename T::M, T::G>), grid_for(C, T::G, kBlock),
                  dim3(kBlock), xlds, m->stream, (const double*)dq, (int)C, (double*)dl, (double*)dg, mc);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(m->ev1, m->stream));
     return (int)EXMC_OK;
   });
+  if (rc) return rc;
+  rc = finish_timing(m);
   if (rc) return rc;
   std::vector<double> hg((size_t)d * C), hl(C);
   HIP_TRY(hipMemcpyAsync(hg.data(), dg, hg.size() * 8, hipMemcpyDeviceToHost, m->stream));
@@ -2329,6 +2334,91 @@ int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, i
   HIP_TRY(hipStreamSynchronize((hipStream_t)0));
   return EXMC_OK;
 #endif
+}
+
+// ---- Pathfinder (include/exmc_hip_pathfinder.h; pathfinder_kernel, exmc_pathfinder.hpp) --------------
+int exmc_hip_pathfinder(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int chain_lo, double* draws_dev,
+                        double* mu_dev, double* sigma_dev, double* elbo_dev, int32_t* num_iters_dev,
+                        int32_t* best_index_dev, int32_t* status_dev) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  static_assert(EXMC_PF_MAX_HISTORY == kPfHistory, "the header states the kernel's bound");
+  if (o.max_iters < 1 || o.num_draws < 1 || o.history_size < 1 || o.history_size > kPfHistory)
+    return fail(EXMC_ERR_BADARG, "pathfinder: max_iters >= 1, num_draws >= 1 and 1 <= history_size <= 6");
+  if (n_paths < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "pathfinder: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  const int lanes = resolve_lanes(m, o.lanes_per_chain);
+  PathfinderParams P;
+  P.n_chains = n_paths;
+  P.chain_lo = chain_lo;
+  P.base_seed = o.seed;
+  P.max_iters = o.max_iters;
+  P.history_size = o.history_size;
+  P.num_draws = o.num_draws;
+  P.entropy_const = 0.5 * m->d * (1.0 + std::log(2.0 * M_PI));   // pathfinder.ex:165, :math.log
+  P.draws = draws_dev;
+  P.mu = mu_dev;
+  P.sigma = sigma_dev;
+  P.elbo = elbo_dev;
+  P.num_iters = num_iters_dev;
+  P.best_index = best_index_dev;
+  P.status = status_dev;
+  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
+  P.nor_r = EXMC_NOR_R;
+  P.flat = flat_order(m);
+  int rc = dispatch(m, lanes, [&](auto tag, const auto& mc) {
+    using T = decltype(tag);
+    const size_t xlds = aux_lds_bytes<typename T::M>();
+    HIP_TRY(hipEventRecord(m->ev0, m->stream));
+    EXMC_KLAUNCH(m->device, (pathfinder_kernel<typename T::M, T::G>), grid_for(n_paths, T::G, kBlock),
+                 dim3(kBlock), xlds, m->stream, P, mc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(m->ev1, m->stream));
+    return (int)EXMC_OK;
+  });
+  if (rc) return rc;
+  return finish_timing(m);   // waits for the launch
+}
+
+int exmc_hip_pathfinder_host(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int chain_lo, double* draws,
+                             double* mu, double* sigma, double* elbo, int32_t* num_iters, int32_t* best_index,
+                             int32_t* status) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  if (o.max_iters < 1 || o.num_draws < 1 || o.history_size < 1 || o.history_size > kPfHistory)
+    return fail(EXMC_ERR_BADARG, "pathfinder: max_iters >= 1, num_draws >= 1 and 1 <= history_size <= 6");
+  if (n_paths < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "pathfinder: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t C = (size_t)n_paths, d = (size_t)m->d, S = (size_t)o.num_draws;
+  // scratch of the call: draws [S][d][C], mu [d][C], sigma [d][C], elbo [C], three int32 [C]
+  const size_t n_dbl = (draws ? S * d * C : 0) + 2 * d * C + C;
+  CallBuf buf;
+  int rc = buf.alloc(n_dbl * 8 + 3 * C * 4);
+  if (rc) return rc;
+  double* d_draws = draws ? buf.as<double>() : nullptr;
+  double* d_mu = buf.as<double>() + (draws ? S * d * C : 0);
+  double* d_sigma = d_mu + d * C;
+  double* d_elbo = d_sigma + d * C;
+  int32_t* d_int = (int32_t*)(d_elbo + C);
+  rc = exmc_hip_pathfinder(m, o, n_paths, chain_lo, d_draws, d_mu, d_sigma, d_elbo, d_int, d_int + C, d_int + 2 * C);
+  if (rc) return rc;
+  std::vector<double> h(n_dbl);
+  std::vector<int32_t> hi(3 * C);
+  HIP_TRY(hipMemcpy(h.data(), buf.p, n_dbl * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hi.data(), d_int, 3 * C * 4, hipMemcpyDeviceToHost));
+  const double* h_mu = h.data() + (draws ? S * d * C : 0);
+  const double* h_sigma = h_mu + d * C;
+  const double* h_elbo = h_sigma + d * C;
+  if (draws) transpose_trace_vec(h.data(), draws, o.num_draws, m->d, n_paths);
+  for (size_t c = 0; c < C; c++) {
+    for (size_t i = 0; i < d; i++) {
+      if (mu) mu[c * d + i] = h_mu[i * C + c];
+      if (sigma) sigma[c * d + i] = h_sigma[i * C + c];
+    }
+    if (elbo) elbo[c] = h_elbo[c];
+    if (num_iters) num_iters[c] = hi[c];
+    if (best_index) best_index[c] = hi[C + c];
+    if (status) status[c] = hi[2 * C + c];
+  }
+  return EXMC_OK;
 }
 
 }  // extern "C"
