@@ -45,6 +45,9 @@ POINTWISE_EXPORTS = ["exmc_hip_pointwise_loglik_range"]
 PATHFINDER_EXPORTS = ["exmc_hip_pathfinder", "exmc_hip_pathfinder_host"]
 PF_MAX_HISTORY = 6
 
+# include/exmc_hip_advi.h: Exmc.ADVI, one mean-field fit per lane group
+ADVI_EXPORTS = ["exmc_hip_advi", "exmc_hip_advi_host"]
+
 
 class ExmcHipError(RuntimeError):
     pass
@@ -62,6 +65,12 @@ class Tuning(C.Structure):
 
 class PfOpts(C.Structure):
     _fields_ = [("num_draws", C.c_int), ("max_iters", C.c_int), ("history_size", C.c_int),
+                ("seed", C.c_uint64), ("lanes_per_chain", C.c_int)]
+
+
+class AdviOpts(C.Structure):
+    _fields_ = [("num_draws", C.c_int), ("max_iters", C.c_int), ("num_mc_samples", C.c_int),
+                ("window_size", C.c_int), ("learning_rate", C.c_double), ("convergence_tol", C.c_double),
                 ("seed", C.c_uint64), ("lanes_per_chain", C.c_int)]
 
 
@@ -167,6 +176,8 @@ def bind(path):
     L.exmc_hip_psis_stats_from_ll.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
     L.exmc_hip_pathfinder.argtypes = [vp, PfOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.exmc_hip_pathfinder_host.argtypes = [vp, PfOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip, ip]
+    L.exmc_hip_advi.argtypes = [vp, AdviOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.exmc_hip_advi_host.argtypes = [vp, AdviOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
     _libs[path] = L
     return L
 

@@ -10,6 +10,7 @@
 #include "../../include/exmc_hip.h"
 #include "../../include/exmc_hip_compare.h"
 #include "../../include/exmc_hip_pathfinder.h"
+#include "../../include/exmc_hip_advi.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2336,6 +2337,31 @@ int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, i
 #endif
 }
 
+// ---- what Pathfinder and ADVI share: one fit per lane group, one launch -----------------------------
+// KERNEL<M, G> of the handle's layout over n lane groups, one wavefront per workgroup (the launch shape of
+// init_chains_kernel), between the handle's events
+#define EXMC_FIT_LAUNCH(m, lanes, KERNEL, n, P)                                                        \
+  dispatch(m, lanes, [&](auto tag, const auto& mc) {                                                   \
+    using T = decltype(tag);                                                                           \
+    const size_t xlds = aux_lds_bytes<typename T::M>();                                                \
+    HIP_TRY(hipEventRecord(m->ev0, m->stream));                                                        \
+    EXMC_KLAUNCH(m->device, (KERNEL<typename T::M, T::G>), grid_for(n, T::G, kBlock), dim3(kBlock),    \
+                 xlds, m->stream, P, mc);                                                              \
+    HIP_TRY(hipGetLastError());                                                                        \
+    HIP_TRY(hipEventRecord(m->ev1, m->stream));                                                        \
+    return (int)EXMC_OK;                                                                               \
+  })
+
+}  // extern "C"
+// a device result [rows][C] (fit the fastest index) into the host's [C][rows]; dst may be null
+template <class T>
+static void fits_first(const T* src, T* dst, size_t rows, size_t C) {
+  if (!dst) return;
+  for (size_t c = 0; c < C; c++)
+    for (size_t i = 0; i < rows; i++) dst[c * rows + i] = src[i * C + c];
+}
+extern "C" {
+
 // ---- Pathfinder (include/exmc_hip_pathfinder.h; pathfinder_kernel, exmc_pathfinder.hpp) --------------
 int exmc_hip_pathfinder(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int chain_lo, double* draws_dev,
                         double* mu_dev, double* sigma_dev, double* elbo_dev, int32_t* num_iters_dev,
@@ -2365,16 +2391,7 @@ int exmc_hip_pathfinder(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int 
   P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
   P.nor_r = EXMC_NOR_R;
   P.flat = flat_order(m);
-  int rc = dispatch(m, lanes, [&](auto tag, const auto& mc) {
-    using T = decltype(tag);
-    const size_t xlds = aux_lds_bytes<typename T::M>();
-    HIP_TRY(hipEventRecord(m->ev0, m->stream));
-    EXMC_KLAUNCH(m->device, (pathfinder_kernel<typename T::M, T::G>), grid_for(n_paths, T::G, kBlock),
-                 dim3(kBlock), xlds, m->stream, P, mc);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(m->ev1, m->stream));
-    return (int)EXMC_OK;
-  });
+  int rc = EXMC_FIT_LAUNCH(m, lanes, pathfinder_kernel, n_paths, P);
   if (rc) return rc;
   return finish_timing(m);   // waits for the launch
 }
@@ -2408,16 +2425,94 @@ int exmc_hip_pathfinder_host(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths,
   const double* h_sigma = h_mu + d * C;
   const double* h_elbo = h_sigma + d * C;
   if (draws) transpose_trace_vec(h.data(), draws, o.num_draws, m->d, n_paths);
-  for (size_t c = 0; c < C; c++) {
-    for (size_t i = 0; i < d; i++) {
-      if (mu) mu[c * d + i] = h_mu[i * C + c];
-      if (sigma) sigma[c * d + i] = h_sigma[i * C + c];
-    }
-    if (elbo) elbo[c] = h_elbo[c];
-    if (num_iters) num_iters[c] = hi[c];
-    if (best_index) best_index[c] = hi[C + c];
-    if (status) status[c] = hi[2 * C + c];
+  fits_first(h_mu, mu, d, C);
+  fits_first(h_sigma, sigma, d, C);
+  fits_first(h_elbo, elbo, 1, C);
+  fits_first(hi.data(), num_iters, 1, C);
+  fits_first(hi.data() + C, best_index, 1, C);
+  fits_first(hi.data() + 2 * C, status, 1, C);
+  return EXMC_OK;
+}
+
+// ---- ADVI (include/exmc_hip_advi.h; advi_kernel, exmc_advi.hpp) --------------------------------------
+static int advi_check(exmc_hip_model* m, const exmc_hip_advi_opts& o, int n_fits, int chain_lo) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  if (o.max_iters < 1 || o.num_draws < 1 || o.num_mc_samples < 1 || o.window_size < 2)
+    return fail(EXMC_ERR_BADARG, "advi: max_iters >= 1, num_draws >= 1, num_mc_samples >= 1 and window_size >= 2");
+  if (n_fits < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "advi: bad arguments");
+  return EXMC_OK;
+}
+
+int exmc_hip_advi(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int chain_lo, double* draws_dev,
+                  double* mu_dev, double* log_sigma_dev, double* elbo_history_dev, int32_t* num_iters_dev,
+                  int32_t* converged_dev) {
+  int rc = advi_check(m, o, n_fits, chain_lo);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const int lanes = resolve_lanes(m, o.lanes_per_chain);
+  // the ELBO window is read back from the history: scratch of the call where the caller wants none
+  CallBuf window;
+  if (!elbo_history_dev) {
+    rc = window.alloc((size_t)o.max_iters * (size_t)n_fits * 8);
+    if (rc) return rc;
   }
+  AdviParams P;
+  P.n_chains = n_fits;
+  P.chain_lo = chain_lo;
+  P.base_seed = o.seed;
+  P.max_iters = o.max_iters;
+  P.num_draws = o.num_draws;
+  P.num_mc_samples = o.num_mc_samples;
+  P.window_size = o.window_size;
+  P.learning_rate = o.learning_rate;
+  P.convergence_tol = o.convergence_tol;
+  P.entropy_const = 0.5 * m->d * (1.0 + std::log(2.0 * M_PI));   // advi.ex:126, :math.log
+  P.history = elbo_history_dev ? elbo_history_dev : window.as<double>();
+  P.fill_history = elbo_history_dev ? 1 : 0;
+  P.draws = draws_dev;
+  P.mu = mu_dev;
+  P.log_sigma = log_sigma_dev;
+  P.num_iters = num_iters_dev;
+  P.converged = converged_dev;
+  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
+  P.nor_r = EXMC_NOR_R;
+  P.flat = flat_order(m);
+  rc = EXMC_FIT_LAUNCH(m, lanes, advi_kernel, n_fits, P);
+  if (rc) return rc;
+  return finish_timing(m);   // waits for the launch: before the window is freed
+}
+
+int exmc_hip_advi_host(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int chain_lo, double* draws,
+                       double* mu, double* log_sigma, double* elbo_history, int32_t* num_iters,
+                       int32_t* converged) {
+  int rc = advi_check(m, o, n_fits, chain_lo);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t C = (size_t)n_fits, d = (size_t)m->d, S = (size_t)o.num_draws, I = (size_t)o.max_iters;
+  // scratch of the call: draws [S][d][C], history [I][C], mu [d][C], log_sigma [d][C], two int32 [C]
+  const size_t n_draws = draws ? S * d * C : 0, n_hist = elbo_history ? I * C : 0;
+  const size_t n_dbl = n_draws + n_hist + 2 * d * C;
+  CallBuf buf;
+  rc = buf.alloc(n_dbl * 8 + 2 * C * 4);
+  if (rc) return rc;
+  double* d_draws = buf.as<double>();
+  double* d_hist = d_draws + n_draws;
+  double* d_mu = d_hist + n_hist;
+  double* d_ls = d_mu + d * C;
+  int32_t* d_int = (int32_t*)(d_ls + d * C);
+  rc = exmc_hip_advi(m, o, n_fits, chain_lo, draws ? d_draws : nullptr, d_mu, d_ls,
+                     elbo_history ? d_hist : nullptr, d_int, d_int + C);
+  if (rc) return rc;
+  std::vector<double> h(n_dbl);
+  std::vector<int32_t> hi(2 * C);
+  HIP_TRY(hipMemcpy(h.data(), buf.p, n_dbl * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hi.data(), d_int, 2 * C * 4, hipMemcpyDeviceToHost));
+  if (draws) transpose_trace_vec(h.data(), draws, o.num_draws, m->d, n_fits);
+  fits_first(h.data() + n_draws, elbo_history, I, C);
+  fits_first(h.data() + n_draws + n_hist, mu, d, C);
+  fits_first(h.data() + n_draws + n_hist + d * C, log_sigma, d, C);
+  fits_first(hi.data(), num_iters, 1, C);
+  fits_first(hi.data() + C, converged, 1, C);
   return EXMC_OK;
 }
 

@@ -239,3 +239,4 @@ __global__ void __launch_bounds__(kNutsBlock) find_eps_kernel(FindEpsParams P,
 
 #include "exmc_gen_pointwise.hpp"   // gen_pointwise_kernel of a plug-in generated with pointwise terms
 #include "exmc_pathfinder.hpp"      // pathfinder_kernel: Exmc.Pathfinder, one L-BFGS path per lane group
+#include "exmc_advi.hpp"            // advi_kernel: Exmc.ADVI, one mean-field fit per lane group
