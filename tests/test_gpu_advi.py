@@ -18,6 +18,11 @@ from exmc_amd import _lib, advi, codegen as cg, models, sampler
 pytestmark = pytest.mark.gpu
 
 KEYS = ("mu", "log_sigma", "elbo_history", "num_iters", "converged", "draws")
+# (kind, lanes): the test that fits in that layout -- each kind's default row; every other row of
+# exmc_layouts.inc is run by test_gpu_fit_layouts.py (test_fit_layouts_catalogue.py holds the two to the table)
+FIT_LAYOUTS = {("simple", 1): "test_simple_one_lane", ("eight_schools", 16): "test_eight_schools_16_lanes",
+               ("sv", 64): "test_sv_64_lanes", ("sv_ncp", 64): "test_sv_ncp_64_lanes",
+               ("logistic", 16): "test_logistic_16_lanes_small_design", ("radon", 64): "test_radon_64_lanes"}
 
 
 def _statement(om, lanes, seed, n_fits, chain_lo=0, **kw):
@@ -92,7 +97,9 @@ def test_sv_ncp_64_lanes(handles):
 
 
 def test_logistic_16_lanes_small_design(handles):
-    """the wave-cooperative model (kCoop, LDS image): lane groups without a fit shadow the last"""
+    """16 lanes: DPL = 2 (d = 21), the butterfly sum, not wave-cooperative: lane groups without a fit
+    return at once. The wave-cooperative model (kCoop) is Logistic<4>:
+    test_gpu_fit_layouts.py::test_logistic_advi at 4 lanes."""
     X, y = models.logistic_data(seed=140, n=40, k=20)
     spec, comp = handles("logistic", lambda: models.logistic(X, y))
     _check(comp, O.model_for(spec), 16, 2, 2, max_iters=8, num_draws=2, window_size=4)
@@ -102,6 +109,12 @@ def test_radon_64_lanes(handles):
     from test_radon_chunks import _survey_like
     spec, comp = handles("radon", lambda: models.radon(_survey_like()))
     _check(comp, O.model_for(spec), 64, 4, 2, max_iters=6, num_draws=2, window_size=4)
+    # at the default rate the density is not finite in the first iterations and mu goes to -inf, which
+    # compares little; at 1e-3 everything stays finite
+    got, want = _check(comp, O.model_for(spec), 64, 4, 2, max_iters=6, num_draws=2, window_size=4,
+                       learning_rate=1.0e-3)
+    assert sum(want["non_finite"]) == 0
+    assert all(np.isfinite(want[k]).all() and np.isfinite(got[k]).all() for k in KEYS)
 
 
 @pytest.fixture(scope="module")

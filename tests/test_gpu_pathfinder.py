@@ -16,6 +16,11 @@ from exmc_amd import codegen as cg, models, pathfinder, sampler
 pytestmark = pytest.mark.gpu
 
 KEYS = ("mu", "sigma", "elbo", "num_iters", "best_index", "status", "draws")
+# (kind, lanes): the test that fits in that layout -- each kind's default row; every other row of
+# exmc_layouts.inc is run by test_gpu_fit_layouts.py (test_fit_layouts_catalogue.py holds the two to the table)
+FIT_LAYOUTS = {("simple", 1): "test_simple_one_lane", ("eight_schools", 16): "test_eight_schools_16_lanes",
+               ("sv", 64): "test_sv_64_lanes", ("sv_ncp", 64): "test_sv_ncp_64_lanes_and_the_halt",
+               ("logistic", 16): "test_logistic_16_lanes_small_design", ("radon", 64): "test_radon_64_lanes"}
 
 
 def _statement(om, lanes, seed, n_paths, chain_lo=0, **kw):
@@ -102,7 +107,9 @@ def test_sv_ncp_64_lanes_and_the_halt(handles):
 
 
 def test_logistic_16_lanes_small_design(handles):
-    """the wave-cooperative model (kCoop, LDS image): lane groups without a path shadow the last"""
+    """16 lanes: DPL = 2 (d = 21), the butterfly sum, not wave-cooperative: lane groups without a path
+    return at once. The wave-cooperative model (kCoop) is Logistic<4>:
+    test_gpu_fit_layouts.py::test_logistic_pathfinder at 4 lanes."""
     X, y = models.logistic_data(seed=140, n=40, k=20)
     spec, comp = handles("logistic", lambda: models.logistic(X, y))
     _check(comp, O.model_for(spec), 16, 2, 2, max_iters=8, num_draws=2)
