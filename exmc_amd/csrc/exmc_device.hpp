@@ -720,6 +720,12 @@ struct Math {
     if constexpr (kVreg) return exmc_log_unit_v(x);
     else return exmc_log_unit(x);
   }
+  // what log_ge1 and log_unit share; each is this value with its own fix-up (exmc_log_ge1_fix,
+  // exmc_log_unit_fix), for a caller that evaluates one argument of each at once (lane_batch)
+  __device__ static __forceinline__ double log_main(double x) {
+    if constexpr (kVreg) return exmc_log_main_v(x);
+    else return exmc_log_main(x);
+  }
   // tree.ex:1597-1605. exp(0) = 1 exactly under exmc_exp, so the larger term is not evaluated.
   // mn - mx <= 0 (or NaN), 1 + exp(.) in [1, 2] (or NaN): the range-restricted forms apply.
   __device__ static __forceinline__ double log_sum_exp(double a, double b) {
@@ -727,6 +733,17 @@ struct Math {
     if (mx == -exmc_from_bits(EXMC_INF_BITS) || mx == -1.0e300) return -1.0e300;
     const double mn = (a > b) ? b : a;
     return mx + log_ge1(1.0 + exp_le0(mn - mx));
+  }
+  // log_sum_exp in two halves, for a caller that evaluates the exponential together with another
+  // one: e = exp_le0(lse_arg(a, b)), then lse_finish(a, b, log_ge1(1.0 + e)) -- the early return is
+  // decided on the same mx, and the exponential of an early-returning pair is evaluated and dropped
+  __device__ static __forceinline__ double lse_arg(double a, double b) {
+    return ((a > b) ? b : a) - ((a > b) ? a : b);
+  }
+  __device__ static __forceinline__ double lse_finish(double a, double b, double log1pe) {
+    const double mx = (a > b) ? a : b;
+    const bool none = (mx == -exmc_from_bits(EXMC_INF_BITS) || mx == -1.0e300);
+    return none ? -1.0e300 : mx + log1pe;
   }
 };
 

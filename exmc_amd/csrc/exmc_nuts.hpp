@@ -968,12 +968,19 @@ struct PairLse {
   template <class MM>
   __device__ __forceinline__ double operator()(MM, double a, double b) const { return MM::log_sum_exp(a, b); }
 };
+// pick(x, lsw) = exp_le0(x), x = b.lsw - lsw: the proposal weight of leaf b, for a caller that evaluates
+// it together with another exponential of the pair's lsw (nuts_run, M::kPassExpPairs)
+struct PairPick {
+  template <class MM>
+  __device__ __forceinline__ double operator()(MM, double x, double) const { return MM::exp_le0(x); }
+};
 
-template <class M, int G, class Lse = PairLse>
+template <class M, int G, class Lse = PairLse, class Pick = PairPick>
 __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const PipeLeaf<M::DPL>& a,
                                                const PipeLeaf<M::DPL>& b, bool pair,
                                                const double (&q0)[M::DPL], const double (&g0)[M::DPL],
-                                               Rng& trng, PipeUnit<M::DPL>& u, Lse&& lse = Lse{}) {
+                                               Rng& trng, PipeUnit<M::DPL>& u, Lse&& lse = Lse{},
+                                               Pick&& pick = Pick{}) {
   constexpr int DPL = M::DPL;
   using MM = Math<M::kVregMath>;
 #pragma unroll
@@ -992,7 +999,7 @@ __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const Pi
   if (pair && !a.div) {
     const double lsw = lse(MM{}, a.lsw, b.lsw);
     const double uu = rng_uniform(trng);
-    const bool use_b = uu < MM::exp_le0(b.lsw - lsw);   // lsw >= b.lsw
+    const bool use_b = uu < pick(MM{}, b.lsw - lsw, lsw);   // lsw >= b.lsw
     bool turning = b.div;
     if (!turning) {
       double rho[DPL];
@@ -1030,47 +1037,78 @@ __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const Pi
 // independent, group-uniform arguments: one evaluation with each argument on a lane of its own
 // (lane_batch; M::kLeafPairExp), the same function on the same bits. lsw_ab is that log_sum_exp,
 // for pipe_pair_unit.
+// M::kPairModelLogs: the second leapfrog needs only the first one's gradient, so both gradient phases
+// of the model run first, then ONE log_ge1 for the two leaves' arguments (lane M::kFinishLane keeps
+// leaf a's, another lane takes leaf b's from it), then both logp finishes and the leaves' scalars.
+// M::kPassExpPairs: a_nx is the lsw the step after this unit merges with (nuts_run). Its
+// log_sum_exp(a_nx, unit's lsw) has its exponential e_nx evaluated here, together with the lone leaf's
+// accept statistic in doubling 0 and with leaf b's proposal weight w_b = exp_le0(b.lsw - lsw_ab) in a pair.
 template <class M, int G>
 __device__ __forceinline__ void leaf_pair(const typename M::Consts& mc, const NutsLane<M, G>& L,
                                           double eps_dir, double jlp0, bool pair,
                                           double (&q)[M::DPL], double (&p)[M::DPL], double (&g)[M::DPL],
                                           double (&q0)[M::DPL], double (&g0)[M::DPL],
-                                          PipeLeaf<M::DPL>& a, PipeLeaf<M::DPL>& b, double& lsw_ab) {
+                                          PipeLeaf<M::DPL>& a, PipeLeaf<M::DPL>& b, double& lsw_ab,
+                                          double a_nx, double& w_b, double& e_nx) {
   constexpr int DPL = M::DPL;
   using MM = Math<M::kVregMath>;
-  // batched_leapfrog.ex:79-85 and tree.ex:1042-1048 without a branch (see pipe_integrate_transition)
-  auto leap = [&](PipeLeaf<DPL>& f) -> double {
+  constexpr bool kSplit = M::kPairModelLogs;
+  typename M::Mid ma, mb;
+  // batched_leapfrog.ex:79-85: the leapfrog, with the model's logp (kSplit: what its finish needs)
+  auto leap = [&](PipeLeaf<DPL>& f, typename M::Mid& m) {
     const double h = eps_dir / 2.0;
 #pragma unroll
     for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
     mass_drift<M, G>(L, eps_dir, p, q);
-    f.logp = M::logp_grad(mc, L.ln, L.l, q, g);
+    if constexpr (kSplit) M::grad_phase(mc, L.ln, L.l, q, g, m);
+    else f.logp = M::logp_grad(mc, L.ln, L.l, q, g);
 #pragma unroll
     for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
-    const double jlp = f.logp - mass_ke<M, G>(L, p);
+#pragma unroll
+    for (int k = 0; k < DPL; k++) { f.q[k] = q[k]; f.p[k] = p[k]; f.g[k] = g[k]; }
+  };
+  // tree.ex:1042-1048 without a branch (see pipe_integrate_transition)
+  auto scalars = [&](PipeLeaf<DPL>& f) -> double {
+    const double jlp = f.logp - mass_ke<M, G>(L, f.p);
     const bool fin = exmc_isfinite(jlp);
     const double dl = jlp - jlp0;
     f.div = fin ? (dl < -1000.0) : true;
     f.lsw = fin ? dl : -1001.0;
-#pragma unroll
-    for (int k = 0; k < DPL; k++) { f.q[k] = q[k]; f.p[k] = p[k]; f.g[k] = g[k]; }
     return fmin(dl, 0.0);
   };
 #pragma unroll
   for (int k = 0; k < DPL; k++) { q0[k] = q[k]; g0[k] = g[k]; }
   double x[3];
-  x[0] = leap(a);
+  leap(a, ma);
   lsw_ab = 0.0;
   if (!pair) {
-    a.acc = a.div ? 0.0 : fmin(1.0, MM::exp_le0(x[0]));
+    if constexpr (kSplit) a.logp = M::logp_finish(mc, L.ln, L.l, ma, MM::log_ge1(M::finish_arg(ma)));
+    x[0] = scalars(a);
+    if constexpr (M::kPassExpPairs && G >= 2) {
+      double y[2] = {x[0], MM::lse_arg(a_nx, a.lsw)};
+      lane_batch<G>(y, L.l, [](double v) { return MM::exp_le0(v); });
+      x[0] = y[0];
+      e_nx = y[1];
+    } else {
+      x[0] = MM::exp_le0(x[0]);
+    }
+    a.acc = a.div ? 0.0 : fmin(1.0, x[0]);
     b = a;
     return;
   }
-  x[1] = leap(b);
+  leap(b, mb);
+  if constexpr (kSplit) {
+    constexpr int K = M::kFinishLane, O = (K == 0) ? 1 : 0;
+    static_assert(G >= 2 && K < G, "two lanes of the group");
+    const double arg_b = group_bcast_c<G, K>(M::finish_arg(mb));
+    const double lg = MM::log_ge1((L.l == O) ? arg_b : M::finish_arg(ma));
+    a.logp = M::logp_finish(mc, L.ln, L.l, ma, lg);
+    b.logp = M::logp_finish(mc, L.ln, L.l, mb, group_bcast_c<G, O>(lg));
+  }
+  x[0] = scalars(a);
+  x[1] = scalars(b);
   // log_sum_exp(a.lsw, b.lsw) with its exponential taken out (Math::log_sum_exp)
-  const double mx = (a.lsw > b.lsw) ? a.lsw : b.lsw;
-  const double mn = (a.lsw > b.lsw) ? b.lsw : a.lsw;
-  x[2] = mn - mx;
+  x[2] = MM::lse_arg(a.lsw, b.lsw);
   if constexpr (M::kLeafPairExp && G >= 3) {
     lane_batch<G>(x, L.l, [](double v) { return MM::exp_le0(v); });
   } else {
@@ -1079,8 +1117,15 @@ __device__ __forceinline__ void leaf_pair(const typename M::Consts& mc, const Nu
   }
   a.acc = a.div ? 0.0 : fmin(1.0, x[0]);
   b.acc = b.div ? 0.0 : fmin(1.0, x[1]);
-  const bool none = (mx == -exmc_from_bits(EXMC_INF_BITS) || mx == -1.0e300);
-  lsw_ab = none ? -1.0e300 : mx + MM::log_ge1(1.0 + x[2]);
+  lsw_ab = MM::lse_finish(a.lsw, b.lsw, MM::log_ge1(1.0 + x[2]));
+  if constexpr (M::kPassExpPairs && G >= 2) {
+    // leaf b's proposal weight (pipe_pair_unit), and the exponential of the step after the unit: the
+    // unit's lsw is lsw_ab, or a.lsw where a diverged first leaf travels alone
+    double y[2] = {b.lsw - lsw_ab, MM::lse_arg(a_nx, a.div ? a.lsw : lsw_ab)};
+    lane_batch<G>(y, L.l, [](double v) { return MM::exp_le0(v); });
+    w_b = y[0];
+    e_nx = y[1];
+  }
 }
 
 // the integrator wave's side of one transition (mirror of nuts_run's skeleton)
@@ -1349,9 +1394,29 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
         double logp_new = 0.0, jlp = 0.0;
         PipeLeaf<DPL> la, lb;
         double lsw_ab = 0.0;
+        // M::kPassExpPairs. Within a pass the ascent is a chain of steps -- the pair unit, the merges at
+        // the trailing-one levels of `leaf`, the outer merge -- and step k's lsw is all that two
+        // exponentials wait for: its own proposal weight exp_le0(c_lsw - lsw) and the one inside the next
+        // step's log_sum_exp(partner, lsw). The partner's lsw is read ahead (the pending node of the next
+        // level, or the trajectory's where the outer merge follows) and step k evaluates both at once,
+        // each on a lane of its own; e_nx carries the second one to the next step. Where nodes park at
+        // the next level no step follows directly and e_nx goes unused: only a turning or diverged node
+        // travels on from there, and the step it reaches evaluates its own exponential (`below`).
+        constexpr bool kExpPairs = kOwnPairs && M::kPassExpPairs && G >= 2 && EXMC_ABLATE == 0;
+        constexpr bool kLogPair = kOwnPairs && M::kOuterLogPair && G >= 2 && EXMC_ABLATE == 0;
+        double e_nx = 0.0, w_b = 0.0;
+        // the lsw the step after level nxt - 1 would merge with
+        auto next_lsw = [&](int nxt) -> double {
+          if (nxt >= nlev) return t_lsw;
+          if (nxt < LDSL) return ((const lds_f64*)(lstk + ((size_t)nxt * NSLOT + kNodeScalars) * kNutsBlock))[0];
+          return gstk[((size_t)(nxt - LDSL) * NSLOT + kNodeScalars) * kNutsBlock];
+        };
+        (void)next_lsw;
         if constexpr (kOwnPairs) {
           // ---- the unit's leapfrogs on every lane, as below ----
-          leaf_pair<M, G>(mc, L, eps_dir, jlp0, depth > 0, q, p, g, qold, gold, la, lb, lsw_ab);
+          double a_nx = 0.0;
+          if constexpr (kExpPairs) a_nx = next_lsw(0);
+          leaf_pair<M, G>(mc, L, eps_dir, jlp0, depth > 0, q, p, g, qold, gold, la, lb, lsw_ab, a_nx, w_b, e_nx);
         } else if constexpr (!Pipe::kOn) {
           // ---- one leapfrog on every lane (batched_leapfrog.ex:79-85); idle groups integrate
           // scratch registers so that wave-cooperative models see all 64 lanes ----
@@ -1391,8 +1456,14 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
               else lb = la;
               pipe_pair_unit<M, G>(L, la, lb, depth > 0, q, g, trng, pu);
             } else {
-              pipe_pair_unit<M, G>(L, la, lb, depth > 0, qold, gold, trng, pu,
-                                   [&](auto, double, double) { return lsw_ab; });
+              if constexpr (kExpPairs) {
+                pipe_pair_unit<M, G>(L, la, lb, depth > 0, qold, gold, trng, pu,
+                                     [&](auto, double, double) { return lsw_ab; },
+                                     [&](auto, double, double) { return w_b; });
+              } else {
+                pipe_pair_unit<M, G>(L, la, lb, depth > 0, qold, gold, trng, pu,
+                                     [&](auto, double, double) { return lsw_ab; });
+              }
             }
 #pragma unroll
             for (int k = 0; k < DPL; k++) {
@@ -1431,6 +1502,10 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
           // ---- ascend (tree.ex:1144-1203, 1390-1476): level lvl holds a pending first half iff
           // bit lvl of `leaf` is set; the first clear bit is where an unfinished node parks ----
           bool parked = false;
+          // kExpPairs: the step directly below level v evaluated that step's exponential iff it was a step --
+          // the pair unit below level 0, a merge (bit v - 1 of `leaf`) elsewhere; wave-uniform
+          const int below = 2 * leaf + 1;
+          (void)below;
           for (int lvl = 0; lvl < nlev; lvl++) {
             if ((leaf >> lvl) & 1) {
               if (!parked) {
@@ -1445,9 +1520,22 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
                 const double u = rng_uniform(trng);
                 const bool use_b = u < 0.5;
 #else
-                const double lsw = MM::log_sum_exp(a_lsw, c_lsw);
-                const double u = rng_uniform(trng);
-                const bool use_b = u < MM::exp_le0(c_lsw - lsw);   // lsw >= c_lsw
+                double lsw, u;
+                bool use_b;
+                if constexpr (kExpPairs) {
+                  // the step below this level evaluated this merge's exponential, unless nodes park there
+                  if (((below >> lvl) & 1) == 0) e_nx = MM::exp_le0(MM::lse_arg(a_lsw, c_lsw));
+                  lsw = MM::lse_finish(a_lsw, c_lsw, MM::log_ge1(1.0 + e_nx));
+                  u = rng_uniform(trng);
+                  double y[2] = {c_lsw - lsw, MM::lse_arg(next_lsw(lvl + 1), lsw)};   // lsw >= c_lsw
+                  lane_batch<G>(y, l, [](double v) { return MM::exp_le0(v); });
+                  use_b = u < y[0];
+                  e_nx = y[1];
+                } else {
+                  lsw = MM::log_sum_exp(a_lsw, c_lsw);
+                  u = rng_uniform(trng);
+                  use_b = u < MM::exp_le0(c_lsw - lsw);   // lsw >= c_lsw
+                }
 #endif
                 if (!use_b) {
                   c_logpP = a_logpP;
@@ -1518,9 +1606,30 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
             const double u = rng_uniform(trng);
             const bool use_sub = u < 0.5;
 #else
-            const double lsw = MM::log_sum_exp(t_lsw, c_lsw);
-            const double u = rng_uniform(trng);
-            const bool use_sub = MM::log_unit(u) < (c_lsw - t_lsw);
+            double lsw, u;
+            bool use_sub;
+            if constexpr (kExpPairs || kLogPair) {
+              // log_sum_exp(t_lsw, c_lsw) in its halves: the exponential comes from the step below
+              // (kExpPairs, unless nodes park there), and its log_ge1 is the main path log_unit(u) has
+              // too -- one evaluation for both arguments, each value with its own fix-up (kLogPair)
+              if (!(kExpPairs && ((below >> nlev) & 1) != 0)) e_nx = MM::exp_le0(MM::lse_arg(t_lsw, c_lsw));
+              u = rng_uniform(trng);
+              double y[2] = {1.0 + e_nx, u};
+              if constexpr (kLogPair) {
+                lane_batch<G>(y, l, [](double v) { return MM::log_main(v); });
+                y[0] = exmc_log_ge1_fix(1.0 + e_nx, y[0]);
+                y[1] = exmc_log_unit_fix(u, y[1]);
+              } else {
+                y[0] = MM::log_ge1(y[0]);
+                y[1] = MM::log_unit(y[1]);
+              }
+              lsw = MM::lse_finish(t_lsw, c_lsw, y[0]);
+              use_sub = y[1] < (c_lsw - t_lsw);
+            } else {
+              lsw = MM::log_sum_exp(t_lsw, c_lsw);
+              u = rng_uniform(trng);
+              use_sub = MM::log_unit(u) < (c_lsw - t_lsw);
+            }
 #endif
             if (use_sub) {
               t_logpP = c_logpP;

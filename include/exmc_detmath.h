@@ -394,6 +394,15 @@ EXMC_HD double exmc_erf(double x) {
   acc_ = (acc_ - hfsq_) + f_;                                                                \
   double res = __builtin_fma(dk_, 6.93147180369123816490e-01, acc_);
 
+/* the fix-ups of the two logarithms, given the main path's value `res` for x: the same in every
+ * spelling of the main path */
+EXMC_HD double exmc_log_ge1_fix(double x, double res) {
+  return res + (x - x);   /* + 0.0 for a finite x (res is never -0), NaN for a NaN */
+}
+EXMC_HD double exmc_log_unit_fix(double x, double res) {
+  return (x == 0.0) ? -exmc_from_bits(EXMC_INF_BITS) : res;
+}
+
 #define EXMC_RANGE_FUNCS(SUFFIX, EXPCORE, LOGCORE)                                           \
   EXMC_RHD double exmc_exp_pm200##SUFFIX(double x) { EXMC_EXP_MAIN(EXPCORE, x) }             \
   EXMC_RHD double exmc_exp_le0##SUFFIX(double x) {                                           \
@@ -402,13 +411,18 @@ EXMC_HD double exmc_erf(double x) {
     const double xc = (x < -746.0) ? -746.0 : x;                                             \
     EXMC_EXP_MAIN(EXPCORE, xc)                                                               \
   }                                                                                          \
-  EXMC_RHD double exmc_log_ge1##SUFFIX(double x) {                                           \
+  /* the main path alone: what exmc_log_ge1 and exmc_log_unit share. A caller with one argument of \
+   * each evaluates it once, each argument on a lane of its own, and applies each value's own    \
+   * fix-up above (exmc_nuts.hpp, the outer merge) */                                         \
+  EXMC_RHD double exmc_log_main##SUFFIX(double x) {                                          \
     EXMC_LOG_MAIN(LOGCORE, x, res)                                                           \
-    return res + (x - x);   /* + 0.0 for a finite x (res is never -0), NaN for a NaN */       \
+    return res;                                                                              \
+  }                                                                                          \
+  EXMC_RHD double exmc_log_ge1##SUFFIX(double x) {                                           \
+    return exmc_log_ge1_fix(x, exmc_log_main##SUFFIX(x));                                    \
   }                                                                                          \
   EXMC_RHD double exmc_log_unit##SUFFIX(double x) {                                          \
-    EXMC_LOG_MAIN(LOGCORE, x, res)                                                           \
-    return (x == 0.0) ? -exmc_from_bits(EXMC_INF_BITS) : res;                                \
+    return exmc_log_unit_fix(x, exmc_log_main##SUFFIX(x));                                   \
   }
 
 #define EXMC_RHD EXMC_HD
