@@ -89,17 +89,14 @@ struct ModelDefaults {
   static constexpr bool kLeafPairs = false;
   static constexpr bool kLeafPairExp = false;
   static constexpr bool kLeanMomentum = false;
-  // Three more lane-batched evaluations of the leaf-pair form's pass (exmc_nuts.hpp nuts_run), each the
+  // Two more lane-batched evaluations of the leaf-pair form's pass (exmc_nuts.hpp nuts_run), each the
   // same function on the same bits. kPassExpPairs: a merge's proposal weight exp_le0(c_lsw - lsw)
   // together with the exponential of the NEXT merge's log_sum_exp (both depend only on lsw), and the lone
-  // leaf's accept statistic together with the outer merge's exponential. kOuterLogPair: the outer merge's
-  // log_unit(u) and the log_ge1 of its log_sum_exp as one main path with two fix-ups. kPairModelLogs: the
-  // model states its evaluation as a gradient phase and a logp finish around one logarithm
-  // (grad_phase / finish_arg / logp_finish), and leaf_pair evaluates the two leaves' logarithms at once.
+  // leaf's accept statistic together with the outer merge's exponential; measured to lose, no model
+  // switches it on ("Round 8"). kOuterLogPair: the outer merge's log_unit(u) and
+  // the log_ge1 of its log_sum_exp as one main path with two fix-ups.
   static constexpr bool kPassExpPairs = false;
   static constexpr bool kOuterLogPair = false;
-  static constexpr bool kPairModelLogs = false;
-  struct Mid {};   // what a model's logp finish takes over from its gradient phase (kPairModelLogs)
 };
 
 // the dynamic LDS of the running kernel (every extern __shared__ array names the same base)
@@ -141,23 +138,12 @@ struct EightSchools : ModelDefaults {
 #define EXMC_ES_PIPE_LEVELS 2
 #endif
   static constexpr int kPipeNutsLevels = (G == 16) ? EXMC_ES_PIPE_LEVELS : 0;
-  // bit 0 kLeafPairs, bit 1 kLeafPairExp, bit 2 kLeanMomentum (to measure each alone)
-#ifndef EXMC_ES_LEAF_PAIRS
-#define EXMC_ES_LEAF_PAIRS 7
-#endif
-  static constexpr bool kLeafPairs = (G == 16) && (EXMC_ES_LEAF_PAIRS & 1);
-  static constexpr bool kLeafPairExp = (G == 16) && (EXMC_ES_LEAF_PAIRS & 2);
-  static constexpr bool kLeanMomentum = (G == 16) && (EXMC_ES_LEAF_PAIRS & 4);
-  // bit 0 kPassExpPairs, bit 1 kOuterLogPair, bit 2 kPairModelLogs (to measure each alone); all three
-  // are pieces of the leaf-pair form. Only kOuterLogPair lowered both the instruction count and the
-  // wave cycles of the timed launch in its own counter run; the other two stay off (DESIGN.md section 5,
-  // "Round 8")
-#ifndef EXMC_ES_PASS_BATCHES
-#define EXMC_ES_PASS_BATCHES 2
-#endif
-  static constexpr bool kPassExpPairs = kLeafPairs && (EXMC_ES_PASS_BATCHES & 1);
-  static constexpr bool kOuterLogPair = kLeafPairs && (EXMC_ES_PASS_BATCHES & 2);
-  static constexpr bool kPairModelLogs = kLeafPairs && (EXMC_ES_PASS_BATCHES & 4);
+  // the leaf-pair form and the pieces of it that were measured to gain, each alone (DESIGN.md section 5,
+  // "Round 7", "Round 8")
+  static constexpr bool kLeafPairs = (G == 16);
+  static constexpr bool kLeafPairExp = (G == 16);
+  static constexpr bool kLeanMomentum = (G == 16);
+  static constexpr bool kOuterLogPair = (G == 16);
   using MM = Math<kVregMath>;
   using Consts = EightSchoolsConsts;
   struct Lane {
@@ -202,11 +188,9 @@ struct EightSchools : ModelDefaults {
   // zmu^2, zmu / 5 on lane 0 and tau / 5, zt^2, zt / 5 on lane 1 ((2 zt) / 5 = 2 (zt / 5) exactly) --
   // and each lane then selects the term and the gradient entry of its own dimension. Same
   // operations on the same operands as the slot form below, so the same bits.
-  // eval_row in two phases. The gradient phase is everything that divides (with_fast_div's watches and
-  // its rare re-evaluation cover exactly it) and leaves in Mid what the finish needs; the finish is the
-  // half-Cauchy term's logarithm -- it feeds lane 1's t_tau and so logp, never the gradient --, T and
-  // the lane-order sum. A caller with two evaluations in hand (leaf_pair, M::kPairModelLogs) runs both
-  // gradient phases, one logarithm for both arguments, and both finishes.
+  // eval_row in two phases, called back to back. The gradient phase is everything that divides and
+  // leaves in Mid what the finish needs; the finish is the half-Cauchy term's logarithm -- it feeds
+  // lane 1's t_tau and so logp, never the gradient --, T and the lane-order sum.
   struct Mid {
     double den, zc, T, lik;   // 1 + zh^2 (lane 1: the logarithm's argument), clamp200(log tau), T without lane 1's term
   };
@@ -272,21 +256,6 @@ struct EightSchools : ModelDefaults {
     Mid m;
     eval_row_grad(c, ln, l, q, g, dv, m);
     return eval_row_finish(c, l, m, MM::log_ge1(m.den));
-  }
-  // the two phases for leaf_pair (the row form only)
-  __device__ static __forceinline__ void grad_phase(const Consts& c, const Lane& ln, int l,
-                                                    const double (&q)[DPL], double (&g)[DPL], Mid& m) {
-    (void)with_fast_div([&](auto& dv) -> double {
-      eval_row_grad(c, ln, l, q, g, dv, m);
-      return 0.0;
-    });
-  }
-  // the logarithm's argument and the lane of the group that holds it
-  static constexpr int kFinishLane = 1;
-  __device__ static __forceinline__ double finish_arg(const Mid& m) { return m.den; }
-  __device__ static __forceinline__ double logp_finish(const Consts& c, const Lane&, int l, const Mid& m,
-                                                       double lg) {
-    return eval_row_finish(c, l, m, lg);
   }
 
   template <class DV>
@@ -1733,10 +1702,8 @@ template <class M>
 struct RowDenseModel : M {
   static constexpr bool kRowDense = true;
   static constexpr bool kPipeWarmup = false;   // the dense warmup is the one-wave form
-  // the pass batches are measured, and switched on, for the diagonal-mass kernel only
-  static constexpr bool kPassExpPairs = false;
+  // the outer merge's log pair is measured, and switched on, for the diagonal-mass kernel only
   static constexpr bool kOuterLogPair = false;
-  static constexpr bool kPairModelLogs = false;
   static_assert(M::DPL == 1 && M::D <= 12, "row layout: one dimension per lane, D <= 12");
 };
 

@@ -1037,9 +1037,6 @@ __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const Pi
 // independent, group-uniform arguments: one evaluation with each argument on a lane of its own
 // (lane_batch; M::kLeafPairExp), the same function on the same bits. lsw_ab is that log_sum_exp,
 // for pipe_pair_unit.
-// M::kPairModelLogs: the second leapfrog needs only the first one's gradient, so both gradient phases
-// of the model run first, then ONE log_ge1 for the two leaves' arguments (lane M::kFinishLane keeps
-// leaf a's, another lane takes leaf b's from it), then both logp finishes and the leaves' scalars.
 // M::kPassExpPairs: a_nx is the lsw the step after this unit merges with (nuts_run). Its
 // log_sum_exp(a_nx, unit's lsw) has its exponential e_nx evaluated here, together with the lone leaf's
 // accept statistic in doubling 0 and with leaf b's proposal weight w_b = exp_le0(b.lsw - lsw_ab) in a pair.
@@ -1052,16 +1049,13 @@ __device__ __forceinline__ void leaf_pair(const typename M::Consts& mc, const Nu
                                           double a_nx, double& w_b, double& e_nx) {
   constexpr int DPL = M::DPL;
   using MM = Math<M::kVregMath>;
-  constexpr bool kSplit = M::kPairModelLogs;
-  typename M::Mid ma, mb;
-  // batched_leapfrog.ex:79-85: the leapfrog, with the model's logp (kSplit: what its finish needs)
-  auto leap = [&](PipeLeaf<DPL>& f, typename M::Mid& m) {
+  // batched_leapfrog.ex:79-85: the leapfrog, with the model's logp
+  auto leap = [&](PipeLeaf<DPL>& f) {
     const double h = eps_dir / 2.0;
 #pragma unroll
     for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
     mass_drift<M, G>(L, eps_dir, p, q);
-    if constexpr (kSplit) M::grad_phase(mc, L.ln, L.l, q, g, m);
-    else f.logp = M::logp_grad(mc, L.ln, L.l, q, g);
+    f.logp = M::logp_grad(mc, L.ln, L.l, q, g);
 #pragma unroll
     for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
 #pragma unroll
@@ -1079,10 +1073,9 @@ __device__ __forceinline__ void leaf_pair(const typename M::Consts& mc, const Nu
 #pragma unroll
   for (int k = 0; k < DPL; k++) { q0[k] = q[k]; g0[k] = g[k]; }
   double x[3];
-  leap(a, ma);
+  leap(a);
   lsw_ab = 0.0;
   if (!pair) {
-    if constexpr (kSplit) a.logp = M::logp_finish(mc, L.ln, L.l, ma, MM::log_ge1(M::finish_arg(ma)));
     x[0] = scalars(a);
     if constexpr (M::kPassExpPairs && G >= 2) {
       double y[2] = {x[0], MM::lse_arg(a_nx, a.lsw)};
@@ -1096,15 +1089,7 @@ __device__ __forceinline__ void leaf_pair(const typename M::Consts& mc, const Nu
     b = a;
     return;
   }
-  leap(b, mb);
-  if constexpr (kSplit) {
-    constexpr int K = M::kFinishLane, O = (K == 0) ? 1 : 0;
-    static_assert(G >= 2 && K < G, "two lanes of the group");
-    const double arg_b = group_bcast_c<G, K>(M::finish_arg(mb));
-    const double lg = MM::log_ge1((L.l == O) ? arg_b : M::finish_arg(ma));
-    a.logp = M::logp_finish(mc, L.ln, L.l, ma, lg);
-    b.logp = M::logp_finish(mc, L.ln, L.l, mb, group_bcast_c<G, O>(lg));
-  }
+  leap(b);
   x[0] = scalars(a);
   x[1] = scalars(b);
   // log_sum_exp(a.lsw, b.lsw) with its exponential taken out (Math::log_sum_exp)

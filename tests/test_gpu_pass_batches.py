@@ -1,15 +1,16 @@
 """The leaf-pair pass of eight_schools at 16 lanes evaluates independent exponentials and logarithms of
-one pass together (exmc_nuts.hpp: M::kPassExpPairs -- a merge's proposal weight with the next merge's
-log_sum_exp exponential, the lone leaf's accept statistic with the outer merge's; M::kOuterLogPair -- the
-outer merge's two logarithms as one main path with two fix-ups; M::kPairModelLogs -- the two model
-logarithms of a leaf pair). Whole transitions through exmc_hip_transitions_host against the checker, bit
-for bit, on all seven trace columns and the final state. Every case first asserts on the checker's own
-output that it shows what it is there for: the longest merge chains of a pass (pair, inner merges at every
-stack level, outer merge), trees ended inside a subtree (a turning node passes the levels at which nodes
-park, so the merges above evaluate their own exponential), divergences in the lone leaf and in either
-leaf of a pair, and non-finite or huge arguments through the doubling-0 batch. 33 chains: the last wave
-has one live lane group. The file runs on the library as built (EXMC_ES_PASS_BATCHES' default); the
-builds with each piece alone and with all three were checked by it once ("Round 8").
+one pass together. What this file guards in the library as built: M::kLeafPairExp -- the three
+exponentials of a leaf pair as one lane-batched evaluation -- and M::kOuterLogPair -- the outer merge's
+two logarithms as one main path with two fix-ups (exmc_nuts.hpp leaf_pair, nuts_run). Whole transitions
+through exmc_hip_transitions_host against the checker, bit for bit, on all seven trace columns and the
+final state. Every case first asserts on the checker's own output that it shows what it is there for: the
+longest merge chains of a pass (pair, inner merges at every stack level, outer merge), trees ended inside
+a subtree (a turning node passes the levels at which nodes park), divergences in the lone leaf and in
+either leaf of a pair, and non-finite or huge arguments through the doubling-0 leaf. 33 chains: the last
+wave has one live lane group. Two more batches were checked by this file once, each alone and together
+with the others ("Round 8"): a merge's proposal weight with the next merge's
+log_sum_exp exponential (M::kPassExpPairs: measured to lose, no model switches it on), and the two model
+logarithms of a leaf pair (measured not to gain; its code is gone from the tree).
 """
 import ctypes as C
 
