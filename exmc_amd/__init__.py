@@ -2,6 +2,7 @@
 
 Package layout: csrc/ (HIP kernels + the C ABI of libexmc_hip.so), sampler.py (host mirror of
 Exmc.NUTS.Sampler), pathfinder.py (host mirror of Exmc.Pathfinder), advi.py (host mirror of Exmc.ADVI),
+predictive.py (host mirror of Exmc.Predictive.posterior_predictive),
 models.py (model kinds of the BASELINE configs), build.py (hipcc driver).
 If torch is going to be used in the same process it must load its HIP runtime first, so it is
 imported here before libexmc_hip.so whenever it is installed.
@@ -11,7 +12,7 @@ try:  # plumbing only: device memory, streams, torch.distributed (RCCL)
 except Exception:  # pragma: no cover
     torch = None
 
-from . import _lib, advi, models, pathfinder, sampler  # noqa: E402,F401
+from . import _lib, advi, models, pathfinder, predictive, sampler  # noqa: E402,F401
 from ._lib import ExmcHipError  # noqa: E402,F401
 
-__all__ = ["advi", "models", "pathfinder", "sampler", "ExmcHipError"]
+__all__ = ["advi", "models", "pathfinder", "predictive", "sampler", "ExmcHipError"]

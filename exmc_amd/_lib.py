@@ -48,6 +48,9 @@ PF_MAX_HISTORY = 6
 # include/exmc_hip_advi.h: Exmc.ADVI, one mean-field fit per lane group
 ADVI_EXPORTS = ["exmc_hip_advi", "exmc_hip_advi_host"]
 
+# include/exmc_hip_predictive.h: Exmc.Predictive.posterior_predictive, one chain's generator per lane
+PREDICTIVE_EXPORTS = ["exmc_hip_posterior_predictive", "exmc_hip_posterior_predictive_host"]
+
 
 class ExmcHipError(RuntimeError):
     pass
@@ -72,6 +75,10 @@ class AdviOpts(C.Structure):
     _fields_ = [("num_draws", C.c_int), ("max_iters", C.c_int), ("num_mc_samples", C.c_int),
                 ("window_size", C.c_int), ("learning_rate", C.c_double), ("convergence_tol", C.c_double),
                 ("seed", C.c_uint64), ("lanes_per_chain", C.c_int)]
+
+
+class PredictiveOpts(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("chain_lo", C.c_int), ("resume", C.c_int)]
 
 
 class Trace(C.Structure):
@@ -178,6 +185,8 @@ def bind(path):
     L.exmc_hip_pathfinder_host.argtypes = [vp, PfOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip, ip]
     L.exmc_hip_advi.argtypes = [vp, AdviOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.exmc_hip_advi_host.argtypes = [vp, AdviOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
+    L.exmc_hip_posterior_predictive.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.exmc_hip_posterior_predictive_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, up, dp]
     _libs[path] = L
     return L
 

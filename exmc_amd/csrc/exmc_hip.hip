@@ -11,6 +11,7 @@
 #include "../../include/exmc_hip_compare.h"
 #include "../../include/exmc_hip_pathfinder.h"
 #include "../../include/exmc_hip_advi.h"
+#include "../../include/exmc_hip_predictive.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2123,6 +2124,60 @@ int ic_dispatch(exmc_hip_model* m, const Src& src, IcMode mode, size_t scratch_b
   return ic_launch(m, src, mode == kIcMatrix, draws, S, C, N, out);
 }
 
+// the source of the handle's kind, handed to f(src) (ic_run, posterior predictive); simple,
+// eight_schools and sv keep their data in the handle's constants, uploaded here for the call: f
+// returns when its kernels have run
+template <class F>
+int ic_with_src(exmc_hip_model* m, F&& f) {
+  const double l2p = log2pi32();
+  std::vector<double> img;
+  if (m->kind == EXMC_MODEL_SIMPLE) img.assign(m->sp.y, m->sp.y + m->sp.n);
+  if (m->kind == EXMC_MODEL_EIGHT_SCHOOLS) {
+    img.assign(m->es.y, m->es.y + 8);
+    img.insert(img.end(), m->es.sg, m->es.sg + 8);
+  }
+  if (m->kind == EXMC_MODEL_SV || m->kind == EXMC_MODEL_SV_NCP) img.assign(m->sv.r, m->sv.r + 100);
+  CallBuf dimg;
+  if (!img.empty()) {
+    int rc = dimg.alloc(img.size() * 8);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(dimg.p, img.data(), img.size() * 8, hipMemcpyHostToDevice));
+  }
+  switch (m->kind) {
+    case EXMC_MODEL_SIMPLE: return f(IcSimpleSrc{dimg.as<double>(), l2p, m->sp.tiny32});
+    case EXMC_MODEL_EIGHT_SCHOOLS: return f(IcEightSchoolsSrc{dimg.as<double>(), l2p});
+    case EXMC_MODEL_SV:
+    case EXMC_MODEL_SV_NCP: {
+      IcSvSrc src{};
+      src.r = dimg.as<double>();
+      for (int i = 0; i < 9; i++) src.lz[i] = m->sv.lanczos[i];
+      src.half_log_2pi32 = m->sv.half_log_2pi32;
+      src.pi32 = m->sv.pi32;
+      src.tiny32 = m->sv.tiny32;
+      src.ncp = m->kind == EXMC_MODEL_SV_NCP;
+      return f(src);
+    }
+    case EXMC_MODEL_LOGISTIC: return f(IcLogisticSrc{m->lg.X, m->lg.y, m->lg.lo, m->lg.hi});
+    case EXMC_MODEL_RADON:
+      return f(IcRadonSrc{m->rd.u, m->rd.cs, m->rd.fl, m->rd.y, m->rd.log2pi32, m->rd.tiny32});
+    default: return fail(EXMC_ERR_UNSUPPORTED, "this model kind has no per-datum terms");
+  }
+}
+
+// posterior predictive replicates of the kind's datums (predictive_kernel, exmc_predictive.hpp): one
+// wavefront per 64 chains, between the handle's events
+template <class Src>
+int predictive_launch(exmc_hip_model* m, const Src& src, const PredictiveParams& P) {
+  const size_t lds = pp_lds_bytes(m->d);
+  if (lds > 64 * 1024) EXMC_KMAXLDS(predictive_kernel<Src>, lds);
+  const unsigned blocks = (unsigned)((P.C + kPpBlock - 1) / kPpBlock);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  hipLaunchKernelGGL(predictive_kernel<Src>, dim3(blocks), dim3(kPpBlock), lds, m->stream, src, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the kernel: before the source's data image is freed
+}
+
 #endif
 
 #ifdef EXMC_GEN_POINTWISE
@@ -2142,8 +2197,7 @@ int gen_pointwise(exmc_hip_model* m, const double* draws, int S, int C, IcRange 
 }
 #endif
 
-// the kind's source of ll over a device trace; simple, eight_schools and sv keep their data in
-// the handle's constants, uploaded here for the call
+// the kind's source of ll over a device trace
 int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, int C, double* out,
            size_t scratch_bytes = 0, IcRange r = IcRange{0, 0}) {
   if (check_model(m)) return EXMC_ERR_BADARG;
@@ -2170,51 +2224,9 @@ int ic_run(exmc_hip_model* m, IcMode mode, const double* draws, int S, int d, in
 #else
   if (mode == kIcPsis && (long long)S * C > kPsisMaxSamples)
     return fail(EXMC_ERR_BADARG, "psis: more than 2^31 - 1 pooled samples");
-  const double l2p = log2pi32();
-  std::vector<double> img;
-  if (m->kind == EXMC_MODEL_SIMPLE) img.assign(m->sp.y, m->sp.y + m->sp.n);
-  if (m->kind == EXMC_MODEL_EIGHT_SCHOOLS) {
-    img.assign(m->es.y, m->es.y + 8);
-    img.insert(img.end(), m->es.sg, m->es.sg + 8);
-  }
-  if (m->kind == EXMC_MODEL_SV || m->kind == EXMC_MODEL_SV_NCP) img.assign(m->sv.r, m->sv.r + 100);
-  CallBuf dimg;
-  if (!img.empty()) {
-    int rc = dimg.alloc(img.size() * 8);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(dimg.p, img.data(), img.size() * 8, hipMemcpyHostToDevice));
-  }
-  int rc = EXMC_OK;
-  switch (m->kind) {
-    case EXMC_MODEL_SIMPLE:
-      rc = ic_dispatch(m, IcSimpleSrc{dimg.as<double>(), l2p, m->sp.tiny32}, mode, scratch_bytes, draws, S, C, N,
-                     out, r);
-      break;
-    case EXMC_MODEL_EIGHT_SCHOOLS:
-      rc = ic_dispatch(m, IcEightSchoolsSrc{dimg.as<double>(), l2p}, mode, scratch_bytes, draws, S, C, N, out, r);
-      break;
-    case EXMC_MODEL_SV:
-    case EXMC_MODEL_SV_NCP: {
-      IcSvSrc src{};
-      src.r = dimg.as<double>();
-      for (int i = 0; i < 9; i++) src.lz[i] = m->sv.lanczos[i];
-      src.half_log_2pi32 = m->sv.half_log_2pi32;
-      src.pi32 = m->sv.pi32;
-      src.tiny32 = m->sv.tiny32;
-      src.ncp = m->kind == EXMC_MODEL_SV_NCP;
-      rc = ic_dispatch(m, src, mode, scratch_bytes, draws, S, C, N, out, r);
-      break;
-    }
-    case EXMC_MODEL_LOGISTIC:
-      rc = ic_dispatch(m, IcLogisticSrc{m->lg.X, m->lg.y, m->lg.lo, m->lg.hi}, mode, scratch_bytes, draws, S, C, N,
-                     out, r);
-      break;
-    case EXMC_MODEL_RADON:
-      rc = ic_dispatch(m, IcRadonSrc{m->rd.u, m->rd.cs, m->rd.fl, m->rd.y, m->rd.log2pi32, m->rd.tiny32}, mode, scratch_bytes,
-                     draws, S, C, N, out, r);
-      break;
-  }
-  return rc;
+  return ic_with_src(m, [&](const auto& src) {
+    return ic_dispatch(m, src, mode, scratch_bytes, draws, S, C, N, out, r);
+  });
 #endif
 }
 
@@ -2514,6 +2526,76 @@ int exmc_hip_advi_host(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int 
   fits_first(hi.data(), num_iters, 1, C);
   fits_first(hi.data() + C, converged, 1, C);
   return EXMC_OK;
+}
+
+// ---- posterior predictive (include/exmc_hip_predictive.h; predictive_kernel, exmc_predictive.hpp) ------
+static int predictive_check(exmc_hip_model* m, const exmc_hip_predictive_opts& o, const void* draws, int n_draws,
+                            int d, int n_chains, const void* rng_state, const void* yrep) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)o; (void)draws; (void)n_draws; (void)d; (void)n_chains; (void)rng_state; (void)yrep;
+  return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive: generated models are not supported");
+#else
+  if (m->kind == EXMC_MODEL_CUSTOM || ic_n_data(m) < 0)
+    return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive: this model kind has no built-in datums");
+  if (!draws || !yrep || d != m->d || n_draws < 1 || n_chains < 1 || o.chain_lo < 0 || (o.resume && !rng_state))
+    return fail(EXMC_ERR_BADARG, "posterior predictive: bad arguments");
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_posterior_predictive(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws_dev,
+                                  int n_draws, int d, int n_chains, uint64_t* rng_state_dev, double* yrep_dev) {
+  int rc = predictive_check(m, o, draws_dev, n_draws, d, n_chains, rng_state_dev, yrep_dev);
+  if (rc) return rc;
+#ifndef EXMC_ONLY_CUSTOM
+  HIP_TRY(hipSetDevice(m->device));
+  PredictiveParams P;
+  P.draws = draws_dev;
+  P.yrep = yrep_dev;
+  P.rng_state = rng_state_dev;
+  P.S = n_draws;
+  P.d = d;
+  P.C = n_chains;
+  P.N = ic_n_data(m);
+  P.chain_lo = o.chain_lo;
+  P.resume = o.resume ? 1 : 0;
+  P.base_seed = o.seed;
+  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
+  P.nor_r = EXMC_NOR_R;
+  rc = ic_with_src(m, [&](const auto& src) { return predictive_launch(m, src, P); });
+#endif
+  return rc;
+}
+
+int exmc_hip_posterior_predictive_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws,
+                                       int n_draws, int d, int n_chains, uint64_t* rng_state, double* yrep) {
+  int rc = predictive_check(m, o, draws, n_draws, d, n_chains, rng_state, yrep);
+  if (rc) return rc;
+#ifndef EXMC_ONLY_CUSTOM
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t S = (size_t)n_draws, C = (size_t)n_chains, D = (size_t)d, N = (size_t)ic_n_data(m);
+  // scratch of the call: draws [S][d][C], yrep [S][N][C], the generators [2][C]
+  std::vector<double> h(S * D * C);
+  for (size_t c = 0; c < C; c++)
+    for (size_t s = 0; s < S; s++)
+      for (size_t j = 0; j < D; j++) h[(s * D + j) * C + c] = draws[(c * S + s) * D + j];
+  CallBuf buf;
+  rc = buf.alloc((S * D * C + S * N * C + 2 * C) * 8);
+  if (rc) return rc;
+  double* d_draws = buf.as<double>();
+  double* d_yrep = d_draws + S * D * C;
+  uint64_t* d_rng = (uint64_t*)(d_yrep + S * N * C);
+  HIP_TRY(hipMemcpy(d_draws, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  if (rng_state && o.resume) HIP_TRY(hipMemcpy(d_rng, rng_state, 2 * C * 8, hipMemcpyHostToDevice));
+  rc = exmc_hip_posterior_predictive(m, o, d_draws, n_draws, d, n_chains, rng_state ? d_rng : nullptr, d_yrep);
+  if (rc) return rc;
+  h.resize(S * N * C);
+  HIP_TRY(hipMemcpy(h.data(), d_yrep, h.size() * 8, hipMemcpyDeviceToHost));
+  transpose_trace_vec(h.data(), yrep, n_draws, (int)N, n_chains);
+  if (rng_state) HIP_TRY(hipMemcpy(rng_state, d_rng, 2 * C * 8, hipMemcpyDeviceToHost));
+#endif
+  return rc;
 }
 
 }  // extern "C"

@@ -83,10 +83,18 @@ __device__ __forceinline__ void ic_lse_merge(double& m, double& s, double m2, do
   }
 }
 
+// ---- the likelihood families of the kinds: what params() of a source returns ---------------------
+// (the parameters of the datum's distribution at a sample: term() takes its ll from them, and
+// exmc_predictive.hpp draws the datum's replicate from them)
+struct NormalParams { double loc, scale; };
+struct BernoulliParams { double p; };            // unclipped
+struct StudentTParams { double df, loc, scale; };
+
 // ---- sources of ll: one struct per kind --------------------------------------------------------
 // consts(q, c): sample t's constants from its parameter row q (one thread per sample);
 // prepare(...): in-place rewrites of the tile (cooperative; may be empty);
-// Datum: what a lane keeps of its datum; load(i) fills it; term(dat, q, c) = ll_i at the sample.
+// Datum: what a lane keeps of its datum; load(i) fills it; params(dat, q, c) = the parameters of the
+// datum's distribution at the sample; term(dat, q, c) = ll_i at the sample.
 struct IcSimpleSrc {
   static constexpr bool kStaged = true;
   const double* y;   // dev [N]
@@ -101,8 +109,10 @@ struct IcSimpleSrc {
     c[2] = log2pi32 + 2.0 * exmc_log(ss);
   }
   __device__ void prepare(double*, const double*, int, int, int, int) const {}
-  __device__ double term(const Datum& a, const double*, const double* c) const {
-    const double z = (a.y - c[0]) / c[1];
+  __device__ NormalParams params(const Datum&, const double*, const double* c) const { return {c[0], c[1]}; }
+  __device__ double term(const Datum& a, const double* q, const double* c) const {
+    const NormalParams p = params(a, q, c);
+    const double z = (a.y - p.loc) / p.scale;
     return -0.5 * (z * z + c[2]);
   }
 };
@@ -121,9 +131,12 @@ struct IcEightSchoolsSrc {
     c[1] = exmc_exp(ic_clamp200(q[1]));
   }
   __device__ void prepare(double*, const double*, int, int, int, int) const {}
+  __device__ NormalParams params(const Datum& a, const double* q, const double* c) const {
+    return {c[0] + c[1] * q[2 + a.j], a.sg};
+  }
   __device__ double term(const Datum& a, const double* q, const double* c) const {
-    const double theta = c[0] + c[1] * q[2 + a.j];
-    const double z = (a.y - theta) / a.sg;
+    const NormalParams p = params(a, q, c);
+    const double z = (a.y - p.loc) / p.scale;
     return -0.5 * (z * z + a.cn);
   }
 };
@@ -174,6 +187,10 @@ struct IcSvSrc {
       }
     }
   }
+  // (term works with exp(-s_t), the reciprocal of this scale, and does not call it)
+  __device__ StudentTParams params(const Datum& a, const double* q, const double* c) const {
+    return {c[2], 0.0, exmc_exp(q[a.t])};
+  }
   __device__ double term(const Datum& a, const double* q, const double* c) const {
     const double s = q[a.t];
     const double z = a.r * exmc_exp(-s);
@@ -202,11 +219,14 @@ struct IcLogisticSrc {
   }
   __device__ void consts(const double*, double*) const {}
   __device__ void prepare(double*, const double*, int, int, int, int) const {}
-  __device__ double term(const Datum& a, const double* q, const double*) const {
+  __device__ BernoulliParams params(const Datum& a, const double* q, const double*) const {
     double eta = q[0];
 #pragma unroll
     for (int j = 0; j < K; j++) eta = __builtin_fma(a.x[j], q[1 + j], eta);
-    const double p = 1.0 / (1.0 + exmc_exp(-eta));
+    return {1.0 / (1.0 + exmc_exp(-eta))};
+  }
+  __device__ double term(const Datum& a, const double* q, const double* c) const {
+    const double p = params(a, q, c).p;
     const double pc = fmin(fmax(p, lo), hi);
     if (a.y == 1.0 || a.y == 0.0) return exmc_log(a.y == 1.0 ? pc : 1.0 - pc);
     return a.y * exmc_log(pc) + (1.0 - a.y) * exmc_log(1.0 - pc);
@@ -245,9 +265,12 @@ struct IcRadonSrc {
       q[j] = (q[J] + q[J + 1] * u[j]) + sa * q[j];
     }
   }
+  __device__ NormalParams params(const Datum& a, const double* q, const double* c) const {
+    return {q[a.j] + c[3] * a.fl, c[1]};
+  }
   __device__ double term(const Datum& a, const double* q, const double* c) const {
-    const double mean = q[a.j] + c[3] * a.fl;
-    const double z = (a.y - mean) / c[1];
+    const NormalParams p = params(a, q, c);
+    const double z = (a.y - p.loc) / p.scale;
     return -0.5 * (z * z + c[2]);
   }
 };

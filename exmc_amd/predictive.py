@@ -1,0 +1,86 @@
+"""Host-side mirror of Exmc.Predictive.posterior_predictive (lib/exmc/predictive.ex:44-63) over the
+device kernel.
+
+    posterior_predictive(compiled, draws, seed=0)  -> (yrep [S][N][C] device tensor, datum names)
+    posterior_predictive_blocks(compiled, draws, block_draws, seed=0) -> yields (s0, yrep block)
+    as_trace(yrep, names)                          -> {name: [C][S] numpy}, the reference's map
+
+The unit is the datum of a built-in kind, as in exmc_amd/model_comparison.py (include/exmc_hip_compare.h):
+one y_i, one return r_t, in the handle's datum order (`names` says which is which). `draws` is the device
+trace [S][d][C] or a host array [C][S][d]. Chain c draws its replicates with one generator seeded with
+seed + 7919 (chain_lo + c), walking the draws and within a draw the datums; the replicates are
+bit-identical to the statement of predictive.ex and its sample/2 callbacks (DESIGN.md "Posterior
+predictive", which states the deviations). The work of a chain is serial by contract, so the throughput
+grows with the number of chains. Generated models are not supported. No CPU fallback."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .diagnostics import _device_trace, _ordered_after_torch
+from .model_comparison import _datum_order, datum_names, n_data
+
+# posterior_predictive refuses matrices above this many bytes: posterior_predictive_blocks walks the draws
+PREDICTIVE_MAX_BYTES = 2 << 30
+
+
+def _names(compiled, N):
+    names = datum_names(compiled)
+    return [names[k] for k in _datum_order(compiled, N)]
+
+
+def _call(compiled, x, s0, ns, seed, chain_lo, resume, state, out):
+    S, d, Cn = x.shape
+    opts = _lib.PredictiveOpts(int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_lo), 1 if resume else 0)
+    compiled.check(compiled.L.exmc_hip_posterior_predictive(
+        compiled.h, opts, x.data_ptr() + s0 * d * Cn * 8, ns, d, Cn,
+        None if state is None else state.data_ptr(), out.data_ptr()))
+
+
+def posterior_predictive(compiled, draws, seed=0, chain_lo=0, max_bytes=PREDICTIVE_MAX_BYTES):
+    """Replicates of every datum at every draw of every chain: a float64 device tensor yrep [S][N][C]
+    in the handle's datum order, and the datum names in that order. Refuses a matrix above max_bytes:
+    posterior_predictive_blocks yields it a block of draws at a time."""
+    import torch
+    N = n_data(compiled)
+    x = _device_trace(compiled, draws)
+    S, d, Cn = x.shape
+    nbytes = S * N * Cn * 8
+    if nbytes > max_bytes:
+        raise ValueError("the replicate matrix would take %.1f GB (limit %.1f GB): use "
+                         "posterior_predictive_blocks, which yields it a block of draws at a time"
+                         % (nbytes / 1e9, max_bytes / 1e9))
+    yrep = torch.empty((S, N, Cn), dtype=torch.float64, device=x.device)
+    _ordered_after_torch(x)
+    _call(compiled, x, 0, S, seed, chain_lo, False, None, yrep)
+    torch.cuda.synchronize(x.device)
+    return yrep, _names(compiled, N)
+
+
+def posterior_predictive_blocks(compiled, draws, block_draws, seed=0, chain_lo=0):
+    """A generator of (s0, yrep_block [ns][N][C]) over the draws in blocks of block_draws, the chains'
+    generators carried from block to block on the device: the blocks joined are posterior_predictive's
+    matrix, bit for bit. Every block is a tensor of its own; the last may be shorter."""
+    import torch
+    if int(block_draws) < 1:
+        raise ValueError("block_draws must be >= 1")
+    N = n_data(compiled)
+    x = _device_trace(compiled, draws)
+    S, d, Cn = x.shape
+    state = torch.zeros((2, Cn), dtype=torch.int64, device=x.device)   # the bits of the uint64 [2][C]
+    _ordered_after_torch(x)
+    for s0 in range(0, S, int(block_draws)):
+        ns = min(int(block_draws), S - s0)
+        out = torch.empty((ns, N, Cn), dtype=torch.float64, device=x.device)
+        _ordered_after_torch(out)
+        _call(compiled, x, s0, ns, seed, chain_lo, s0 > 0, state, out)
+        torch.cuda.synchronize(x.device)
+        yield s0, out
+
+
+def as_trace(yrep, names):
+    """{name: [C][S]}: the reference's %{obs_name => {n}} per chain, from yrep [S][N][C]"""
+    a = yrep.cpu().numpy() if hasattr(yrep, "cpu") else np.asarray(yrep)
+    if a.ndim != 3 or a.shape[1] != len(names):
+        raise ValueError("yrep must be [S][N][C] with one name per datum")
+    return {name: np.ascontiguousarray(a[:, i, :].T) for i, name in enumerate(names)}

@@ -1,0 +1,171 @@
+"""The statement of posterior predictive sampling (tests/predictive_statement.py) on the CPU: its samplers
+draw from the distributions they name; the inputs of the GPU parity test take every branch of the
+samplers and never reach the gamma cap; hostile traces terminate; the NIF table names what the Elixir
+stub names."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import predictive_inputs as PI
+import predictive_statement as PS
+import test_elixir_sources as ES
+from exmc_amd import models
+
+N_MOMENTS = 20000
+
+
+def _moments(v):
+    v = np.asarray(v)
+    return float(v.mean()), float(v.var(ddof=1))
+
+
+def test_normal_replicates_have_the_mean_and_variance():
+    g = PS.Gen(seed=11)
+    loc, scale = 1.5, 2.0
+    v = [PS.sample_normal(loc, scale, g) for _ in range(N_MOMENTS)]
+    mean, var = _moments(v)
+    assert abs(mean - loc) <= 5 * scale / math.sqrt(N_MOMENTS)
+    # the variance of a normal sample's variance is 2 sigma^4 / (n - 1)
+    assert abs(var - scale ** 2) <= 5 * scale ** 2 * math.sqrt(2.0 / (N_MOMENTS - 1))
+
+
+def test_bernoulli_replicates_have_the_mean_and_variance():
+    g = PS.Gen(seed=12)
+    p = 0.3
+    v = [PS.sample_bernoulli(p, g) for _ in range(N_MOMENTS)]
+    assert set(v) == {0.0, 1.0}
+    mean, var = _moments(v)
+    assert abs(mean - p) <= 5 * math.sqrt(p * (1 - p) / N_MOMENTS)
+    # Var(s^2) ~ (mu4 - sigma^4) / n with mu4 = p q (1 - 3 p q)
+    pq = p * (1 - p)
+    assert abs(var - pq) <= 5 * math.sqrt((pq * (1 - 3 * pq) - pq ** 2) / N_MOMENTS)
+    assert PS.sample_bernoulli(math.nan, g) == 0.0
+
+
+def test_student_t_replicates_have_the_mean():
+    g = PS.Gen(seed=13)
+    df, loc, scale = 10.0, 0.5, 1.5
+    v = [PS.sample_student_t(df, loc, scale, g) for _ in range(N_MOMENTS)]
+    mean, _ = _moments(v)
+    sd = scale * math.sqrt(df / (df - 2.0))
+    assert abs(mean - loc) <= 5 * sd / math.sqrt(N_MOMENTS)
+    assert g.n["cap"] == 0 and g.n["boost"] == 0 and g.n["gamma_log_reject"] > 0
+
+
+def test_gamma_has_the_mean_on_both_sides_of_the_boost():
+    for alpha, seed in ((0.4, 14), (3.0, 15)):
+        g = PS.Gen(seed=seed)
+        v = [PS.sample_gamma(alpha, 0.5, g) for _ in range(N_MOMENTS)]
+        mean, _ = _moments(v)
+        assert abs(mean - alpha / 0.5) <= 5 * math.sqrt(alpha / 0.25 / N_MOMENTS), alpha
+        assert (g.n["boost"] == N_MOMENTS) == (alpha < 1.0)
+
+
+def test_the_cap_ends_a_loop_that_never_accepts():
+    g = PS.Gen(seed=16)
+    before = g.state()
+    assert math.isnan(PS.sample_gamma(math.nan, 0.5, g))       # every log test compares with NaN
+    assert g.n["cap"] == 1 and g.n["gamma_log_reject"] == PS.GAMMA_CAP and g.n["boost"] == 1
+    assert g.state() != before                                   # ... and the generator has moved on
+    assert 0.0 <= g.uniform() < 1.0
+
+
+def test_scan_restates_the_walk_of_sv_ncp():
+    import sv_ncp_checker as NC
+    q = np.random.default_rng(5).normal(size=102)
+    sigma = PS._exp(PS.clamp200(float(q[100])))
+    s = PS.scan_fwd64([float(q[0]) if i == 0 else (sigma * float(q[i]) if i < 100 else 0.0) for i in range(128)])
+    assert np.array(s[:100]).tobytes() == NC.walk(q, dev=True).tobytes()
+
+
+def test_parity_inputs_take_every_branch_and_never_the_cap():
+    total = PS.new_counters()
+    for kind in PI.KINDS:
+        x, yrep, states, n = PI.expected(kind)
+        assert x.shape == (PI.S_PAR, PI.spec(kind).d, PI.C_PAR)
+        assert yrep.shape == (PI.S_PAR, PS.n_data(kind, PI.spec(kind).data), PI.C_PAR)
+        assert np.isfinite(yrep).all(), kind
+        assert n["cap"] == 0, kind
+        for k in total:
+            total[k] += n[k]
+        if kind in (models.SV, models.SV_NCP):
+            # the chains around nu = 0.3 boost, the others (nu around 10) do not
+            nu = np.exp(x[:, 101, :])
+            assert (nu[:, :PI.LOW_NU_CHAINS] < 2.0).all() and (nu[:, PI.LOW_NU_CHAINS:] >= 2.0).all()
+            assert n["boost"] == PI.S_PAR * 100 * PI.LOW_NU_CHAINS
+            for k in ("zig_wedge", "gamma_v_reject", "gamma_log_reject"):
+                assert n[k] > 0, (kind, k)
+        if kind == models.LOGISTIC:
+            assert set(np.unique(yrep)) == {0.0, 1.0}
+    for k in PS.COUNTERS:
+        assert (total[k] > 0) == (k != "cap"), (k, total)
+
+
+@pytest.mark.parametrize("kind", PI.KINDS)
+def test_hostile_traces_terminate(kind):
+    x, yrep, states, n = PI.expected(kind, "hostile")
+    assert not np.isfinite(x).all()
+    assert yrep.shape[2] == x.shape[2]
+    if kind != models.LOGISTIC:          # a Bernoulli replicate of a NaN p is 0.0
+        assert not np.isfinite(yrep).all()
+    # chains whose rows were left alone equal the same chains of a clean run
+    clean = PS.run(kind, PI.spec(kind).data, PI.draws(kind, 2, 70)[:, :, :3], seed=PI.SEED, chain_lo=PI.CHAIN_LO)[0]
+    assert clean.tobytes() == np.ascontiguousarray(yrep[:, :, :3]).tobytes()
+
+
+def test_continuation_of_the_statement():
+    kind = models.SV
+    x = PI.draws(kind, 3, 4)
+    blob = PI.spec(kind).data
+    whole, st, _ = PS.run(kind, blob, x, seed=5, chain_lo=1)
+    a, sa, _ = PS.run(kind, blob, x[:1], seed=5, chain_lo=1)
+    b, sb, _ = PS.run(kind, blob, x[1:], states=sa)
+    assert np.concatenate([a, b]).tobytes() == whole.tobytes() and sb.tobytes() == st.tobytes()
+
+
+# ---- the BEAM side as source files -----------------------------------------------------------------
+C_SRC = os.path.join(ES.ROOT, "c_src", "exmc_hip_predictive_nif.c")
+
+
+def test_nif_table_equals_the_elixir_stub():
+    c = open(C_SRC).read()
+    rows = re.findall(r'\{"(\w+)", (\d+), (\w+), (\w+)\}', c[c.index("static ErlNifFunc nif_funcs[]"):])
+    assert rows == [("posterior_predictive", "6", "posterior_predictive", "ERL_NIF_DIRTY_JOB_IO_BOUND")]
+    assert "ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPredictiveNative," in c
+    ex = ES._read(ES.EX, "lib", "exmc", "nuts", "hip_predictive_native.ex")
+    assert "defmodule Exmc.NUTS.HipPredictiveNative do" in ex and "@on_load :load_nif" in ex
+    assert ":erlang.load_nif" in ex and "exmc_hip_predictive_nif" in ex
+    stubs = {m.group(1): len(ES._split_args(m.group(2))) for m in re.finditer(
+        r"def\s+([a-z_]+)\(([^)]*)\)\s*,?\s*do:\s*:erlang\.nif_error\(:nif_not_loaded\)", ES._strip(ex))}
+    assert stubs == {"posterior_predictive": 6}
+
+
+def test_wrapper_calls_the_stub_with_its_arity():
+    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", "hip_predictive.ex"))
+    m = re.search(r"HipPredictiveNative\.posterior_predictive\(", src)
+    i, depth = m.end(), 1
+    while depth:
+        depth += {"(": 1, ")": -1}.get(src[i], 0)
+        i += 1
+    assert len(ES._split_args(src[m.end():i - 1])) == 6
+    assert "def posterior_predictive(" in src
+
+
+@pytest.mark.parametrize("name", ["hip_predictive_native.ex", "hip_predictive.ex"])
+def test_blocks_balance(name):
+    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", name))
+    opens = len(re.findall(r"\bdo\b(?!:)", src)) + len(re.findall(r"\bfn\b", src))
+    assert opens == len(re.findall(r"\bend\b", src)), name
+    for a, b in ("()", "[]", "{}"):
+        assert src.count(a) == src.count(b), (name, a)
+    assert src.lstrip().startswith("defmodule Exmc.NUTS.")
+
+
+def test_shim_compiles_against_the_declaration_header(tmp_path):
+    import subprocess
+    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-c", "-o",
+                           str(tmp_path / "nif.o"), C_SRC])
+    assert "exmc_hip_predictive_nif" in open(os.path.join(ES.ROOT, "INTEGRATION.md")).read()
