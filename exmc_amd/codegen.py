@@ -44,7 +44,22 @@ Numeric contract of the generated code:
     (tests/gen_checker.py), not a hand-derived gradient.
   * everything that depends only on the model's data is evaluated once on the host at
     exmc_hip_model_create (exmc_gen_fold) and read by the kernels through uniform scalar loads.
+
+`generate` is a list of stages, each a function of this module:
+  rewrite, _apply_ncp            the IR passes
+  _layout                        the free variables in the flat position (-> _Layout), lanes
+  _Resolver                      params and values as graph nodes; owns the graph
+  _terms                         one term per node in _term_ids order: _rv_term, _meas_obs_term
+                                 (_meas_inverse), _obs_term (_obs_custom, _obs_vector_dist,
+                                 _obs_censored, _obs_elementwise), the obs meta and what a datum is
+                                 in _obs_meta; _sum_logps adds them up
+  _one_lane_section, _plate_section, _lane_section, _pointwise_section
+                                 the header and the data array, section by section (_emit,
+                                 codegen_vec, codegen_lanes, _emit_pointwise) -> Generated
+The graph numbers its nodes in creation order and the text follows the numbers, so the order in
+which the stages create nodes is part of the output (tests/test_codegen_text_pinned.py).
 """
+import dataclasses
 import hashlib
 import math
 import os
@@ -842,9 +857,26 @@ class Ops:
 # ---------------------------------------------------------------------------------------------
 # the term walk
 # ---------------------------------------------------------------------------------------------
+@dataclasses.dataclass(eq=False, repr=False)
 class Generated:
-    """d, var_names (flat order, point_map.ex:37), transforms, ncp_info, data (what
-    exmc_hip_model_create receives), header (the generated source) and its digest."""
+    """What `generate` returns: the flat layout (point_map.ex:37), what exmc_hip_model_create
+    receives (`data`), the generated source (`header`) and its digest."""
+    d: int
+    var_names: list            # flat order
+    vector_entries: dict       # id -> (first flat slot, length)
+    simplex_entries: dict      # the Dirichlet ones: K - 1 flat slots each, a K-vector in the trace
+    transforms: dict
+    ncp_info: dict
+    lanes: int
+    vec: object                # codegen_vec.generate's result, when the model has the plate layout
+    lane_layout: object        # codegen_lanes.generate's result, when it has the lane layout
+    data: np.ndarray
+    header: str
+    scan_chains: list
+    datum_names: object        # pointwise only, else None
+    n_datums: int              # pointwise only, else -1
+    digest: str                # of the header: the plug-in cache's tag
+    n_ops: int
 
 
 def _observed_targets(ir):
@@ -915,6 +947,427 @@ def _apply_ncp(ir, ncp):
 PW_GROUP = 16   # datums per generated function of the pointwise section (_emit_pointwise)
 
 
+class _Layout:
+    """The free variables in the flat position: PointMap.build (point_map.ex:30-60), entries sorted
+    by id, each `length` flat slots; `lanes` as asked for or as the dimension decides."""
+    __slots__ = ("free", "offset", "length", "flat_names", "vector_entries", "lanes", "one_lane")
+
+
+def _layout(ir, nodes, lanes):
+    for id_, n in nodes.items():
+        if n["op"] == "obs" and n["target"] not in nodes:
+            raise CodegenError("obs %r targets unknown node %r" % (id_, n["target"]))
+    observed = _observed_targets(ir)
+    lay = _Layout()
+    lay.free = sorted(i for i, n in nodes.items() if n["op"] == "rv" and i not in observed)
+    if not lay.free:
+        raise CodegenError("no free random variables")
+    lay.offset, lay.length, lay.flat_names, lay.vector_entries = {}, {}, [], {}
+    for id_ in lay.free:
+        n = nodes[id_]
+        ln = _vector_length(id_, n) if n["dist"] in VECTOR_DISTS else 1
+        if n["dist"] in VECTOR_DISTS and n["transform"] is not None and n["dist"] != "dirichlet":
+            raise CodegenError("a transformed vector rv is not covered")
+        lay.offset[id_], lay.length[id_] = len(lay.flat_names), ln
+        if n["dist"] in VECTOR_DISTS:
+            lay.vector_entries[id_] = (len(lay.flat_names), ln)
+            lay.flat_names.extend("%s[%d]" % (id_, i) for i in range(ln))
+        else:
+            lay.flat_names.append(id_)
+    d = len(lay.flat_names)
+    if d > MAX_D_LANES:
+        raise CodegenError("%d free dimensions; the kernels take at most %d" % (d, MAX_D_LANES))
+    if lanes is None and d > MAX_D:
+        lanes = 64 if d > 32 else 16
+    if lanes is not None and lanes not in (16, 32, 64):
+        raise CodegenError("lanes must be 16, 32 or 64")
+    lay.lanes, lay.one_lane = lanes, d <= MAX_D
+    return lay
+
+
+class _Resolver:
+    """Params and values as graph nodes (resolve_params_constrained, compiler.ex:436-463). It owns the
+    graph and notes what the lane layout asks about later: `ncp_nodes`, non-centred id -> its node
+    mu + sigma * z (the scan chains), and `custom_roots`, the terms that are the result of a Custom
+    closure (a hand-written reduction)."""
+
+    def __init__(self, nodes, data_tensor, layout, ncp_info):
+        self.g = _Graph()
+        self.nodes, self.data_tensor, self.lay, self.ncp_info = nodes, data_tensor, layout, ncp_info
+        self.ncp_nodes, self.custom_roots = {}, set()
+        self.ops = Ops(self.g)
+
+    def ref(self, id_, stack=()):
+        # compiler.ex:447-463
+        g, lay = self.g, self.lay
+        if id_ not in lay.offset:
+            raise CodegenError("param ref %r is not a free random variable" % id_)
+        if id_ in stack:
+            raise CodegenError("cyclic non-centred reference through %r" % id_)
+        if id_ in lay.vector_entries:
+            zs = [g.q(lay.offset[id_] + i) for i in range(lay.length[id_])]
+            return _stick_breaking_forward(g, zs) if self.nodes[id_]["dist"] == "dirichlet" else zs
+        z = g.q(lay.offset[id_])
+        if id_ in self.ncp_info:
+            mu = self.value(self.ncp_info[id_]["mu"], stack + (id_,))
+            sigma = self.value(self.ncp_info[id_]["sigma"], stack + (id_,))
+            self.ncp_nodes[id_] = g.add(mu, g.mul(sigma, z))
+            return self.ncp_nodes[id_]
+        return _apply_transform(g, self.nodes[id_]["transform"], z)
+
+    def value(self, v, stack=()):
+        g = self.g
+        if isinstance(v, str) and v == "__obs_data":       # compiler.ex:114-118: the IR's data tensor
+            t = self.data_tensor
+            if t is None:
+                raise CodegenError('"__obs_data" is referenced but the IR has no data (Builder.data)')
+            if t.ndim == 2:
+                return [[g.datum(float(x)) for x in row] for row in t]
+            return g.datum(float(t)) if t.ndim == 0 else [g.datum(float(x)) for x in t]
+        if isinstance(v, str):
+            return self.ref(v, stack)
+        if isinstance(v, F32):
+            return g.datum32(v)
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            return g.datum(float(a))
+        if a.ndim == 1:
+            return [g.datum(float(x)) for x in a]
+        raise CodegenError("params are scalars, vectors or refs")
+
+    def params(self, dist, params):
+        if dist == "mixture":     # nested: one params map per component, a weight vector
+            cps = [self.params(c, pp) for c, pp in zip(params.get("components", []), params.get("params", []))]
+            ws = self.value(params.get("weights"))
+            return dict(components=list(params.get("components", [])), params=cps,
+                        weights=ws if isinstance(ws, list) else [ws])
+        return {k: self.value(v) for k, v in params.items()}
+
+    def elementwise(self, dist, x, params):
+        """-> (elems, is_vec): the logpdf broadcast over a vector value and vector params"""
+        g = self.g
+        if dist == "mixture":     # scalar params per component; only the value may be a vector
+            if isinstance(x, list):
+                return [_logpdf(g, dist, xi, params) for xi in x], True
+            return _logpdf(g, dist, x, params), False
+        n = max([len(v) for v in [x] + list(params.values()) if isinstance(v, list)] + [0])
+        if n == 0:
+            return _logpdf(g, dist, x, params), False
+        for v in [x] + list(params.values()):
+            if isinstance(v, list) and len(v) != n:
+                raise CodegenError("vector lengths differ")
+        pick = lambda v, i: v[i] if isinstance(v, list) else v   # noqa: E731
+        return [_logpdf(g, dist, pick(x, i), {k: pick(v, i) for k, v in params.items()})
+                for i in range(n)], True
+
+    def custom_logpdf(self, params, x):
+        fn = params.get("logpdf")
+        if not callable(fn):
+            raise CodegenError("a custom distribution needs a callable 'logpdf'")
+        rest = {k: self.value(v) for k, v in params.items() if k != "logpdf"}
+        t = fn(self.ops, x, rest)
+        if isinstance(t, list):
+            raise CodegenError("a custom logpdf must return a scalar (reduce inside the closure)")
+        self.custom_roots.add(t)
+        return t
+
+    def const_x(self, tr, v, id_):
+        # compiler.ex:284-291, 327-334, 350-357: z = inverse_transform(value), x = Transform.apply(z),
+        # the log-Jacobian at z joins the term (all constants of the data). v: a float or a node.
+        g = self.g
+        d = v if isinstance(v, int) else g.datum(float(v))
+        if tr is None:
+            return d, None
+        if tr == "log":
+            z = g.log(d)
+        elif tr == "softplus":
+            if isinstance(v, int):
+                raise CodegenError("%r: a softplus-transformed target of a computed value is not covered" % id_)
+            z = g.datum(math.log(math.expm1(float(v))))      # Nx.log(Nx.expm1(x)), host libm
+        elif tr == "logit":
+            z = g.sub(g.log(d), g.log1p(g.neg(d)))
+        else:
+            raise CodegenError("%r: an observation of a %r-transformed rv is not covered" % (id_, tr))
+        return _apply_transform(g, tr, z), _log_abs_det_jacobian(g, tr, z)
+
+
+def _term_ids(ir, nodes):
+    """The ids in Map.values order (compiler.ex:176-180): the exported order where the IR has one
+    and it fits the node map, else sorted."""
+    term_order = getattr(ir, "term_order", None)
+    if term_order is None:
+        return sorted(nodes)
+    if sorted(term_order) != sorted(nodes) or len(term_order) != len(nodes):
+        raise CodegenError("term_order does not match the node map")   # (a rewrite pass changed the key set)
+    if len(nodes) <= MAX_NODES_SORTED and list(term_order) != sorted(nodes):
+        raise CodegenError("term_order of a map of <= %d keys must be the sorted ids (Erlang flatmaps "
+                           "are sorted)" % MAX_NODES_SORTED)
+    return term_order
+
+
+def _rv_term(r, id_, n):
+    """The term of a free rv: its logpdf at the constrained value + log|J| (compiler.ex:222-229)."""
+    g, lay = r.g, r.lay
+    if n["dist"] in VECTOR_DISTS:
+        xs = [g.q(lay.offset[id_] + i) for i in range(lay.length[id_])]
+        if n["dist"] == "dirichlet":              # logpdf on the simplex + log|J|
+            t = _logpdf_vector(g, "dirichlet", _stick_breaking_forward(g, xs), n["params"], r.value)
+            return g.add(t, _stick_breaking_ladj(g, xs))
+        return _logpdf_vector(g, n["dist"], xs, n["params"], r.value)
+    z = g.q(lay.offset[id_])
+    x = _apply_transform(g, n["transform"], z)
+    if n["dist"] == "custom":
+        t = r.custom_logpdf(n["params"], x)
+    else:
+        params = r.params(n["dist"], n["params"])
+        if n["dist"] != "mixture" and any(isinstance(v, list) for v in params.values()):
+            raise CodegenError("free RV %r has a vector param" % id_)
+        t = _logpdf(g, n["dist"], x, params)
+    if n["transform"] is not None:
+        t = g.add(t, _log_abs_det_jacobian(g, n["transform"], z))
+    return t
+
+
+def _plus(g, t, j):
+    """t + j where t may be a vector (a list): element by element, a scalar j broadcast."""
+    if isinstance(t, list):
+        return [g.add(e, j[i] if isinstance(j, list) else j) for i, e in enumerate(t)]
+    return g.add(t, j)
+
+
+def _meas_inverse(g, val, info):
+    """-> (x, jac) of a meas_obs: the target's value x = (y - b) / a or A^-1 y and the measurable
+    function's log-Jacobian, a scalar or (a vector `a`) one per element (compiler.ex:342-369)."""
+    if info[0] == "affine":
+        av, bv = np.asarray(info[1], dtype=np.float64), np.asarray(info[2], dtype=np.float64)
+        at = lambda c, i: g.datum(float(c if c.ndim == 0 else c[i]))   # noqa: E731
+        conv = lambda v, i: g.div(g.sub(g.datum(float(v)), at(bv, i)), at(av, i))   # noqa: E731
+        x = conv(val, 0) if val.ndim == 0 else [conv(v, i) for i, v in enumerate(val)]
+        if av.ndim == 0:
+            return x, g.neg(g.log(g.abs(g.datum(float(av)))))
+        return x, [g.neg(g.log(g.abs(g.datum(float(c))))) for c in av]
+    sol = np.linalg.solve(info[1], val)                  # jit_solve: third-party LinAlg
+    x = [g.datum(float(v)) for v in sol]
+    return x, g.datum(-math.log(abs(float(np.linalg.det(info[1])))))
+
+
+def _meas_obs_term(r, id_, n):
+    """compiler.ex:258-266, 342-369: eager -- the target's params are used as written (no refs), so
+    the whole term is a constant of the data (and no datum of the pointwise section)."""
+    g = r.g
+    tgt = r.nodes[n["target"]]
+    if tgt["op"] != "rv" or tgt["dist"] in VECTOR_DISTS + ("custom",):
+        raise CodegenError("meas_obs %r: target not covered" % id_)
+    if any(isinstance(v, str) for v in tgt["params"].values()):
+        raise CodegenError("meas_obs %r: the reference evaluates it eagerly, params must be constants" % id_)
+    params = r.params(tgt["dist"], tgt["params"])
+    tr = tgt["transform"]
+    x, jac = _meas_inverse(g, n["value"], n["info"])
+    tjac = None
+    if tr is not None:                    # compiler.ex:350-359, 371-382: (logp + jac) + meas_jac
+        pairs = [r.const_x(tr, v, id_) for v in (x if isinstance(x, list) else [x])]
+        x = [p_[0] for p_ in pairs] if isinstance(x, list) else pairs[0][0]
+        tjac = [p_[1] for p_ in pairs]
+    t, vec = r.elementwise(tgt["dist"], x, params)
+    # logpdf of a vector value is a vector; combined = logp + jac broadcasts, the meta's reduce (or,
+    # without one, sum_logps' Nx.sum, compiler.ex:396-397) folds it
+    if tjac is not None:
+        t = _plus(g, t, tjac if len(tjac) > 1 else tjac[0])
+    t = _plus(g, t, jac)
+    meta = dict(n.get("meta") or {})
+    if vec and meta.get("reduce") is None:
+        meta["reduce"] = "sum"
+    return _obs_meta(g, t, vec, meta, id_)[0]
+
+
+# the four kinds of obs term, each -> (elems, is_vec): a node, or one node per element
+def _obs_custom(r, tgt, val, vec):
+    x = [r.g.datum(float(v)) for v in val] if vec else r.g.datum(float(val))
+    return r.custom_logpdf(tgt["params"], x), False
+
+
+def _obs_vector_dist(r, id_, tgt, val, cens):
+    g, tr = r.g, tgt["transform"]
+    if val.ndim != 1 or cens:
+        raise CodegenError("obs %r of a vector distribution needs a plain vector value" % id_)
+    xs, jac = [g.datum(float(v)) for v in val], None
+    if tr == "stick_breaking":        # compiler.ex:424: z from the datum, the point rebuilt from z
+        zs = [g.datum(float(v)) for v in inverse_stick_breaking(val)]
+        xs, jac = _stick_breaking_forward(g, zs), _stick_breaking_ladj(g, zs)
+    elif tr is not None:
+        raise CodegenError("obs %r: transform %r on a vector distribution is not covered" % (id_, tr))
+    t = _logpdf_vector(g, tgt["dist"], xs, tgt["params"], r.value)
+    return (t if jac is None else g.add(t, jac)), False
+
+
+def _obs_censored(r, id_, tgt, val, cens, vec):
+    g = r.g
+    params = r.params(tgt["dist"], tgt["params"])
+    if any(isinstance(v, list) for v in params.values()):
+        raise CodegenError("censored obs %r: vector params are not covered" % id_)
+    def bound(row):
+        return (g.datum(float(row[0])), g.datum(float(row[1]))) if cens == "interval" else g.datum(float(row))
+    out = [_censored_loglik(g, cens, bound(row), tgt["dist"], params) for row in (val if vec else val[None, ...])]
+    return (out, True) if vec else (out[0], False)
+
+
+def _obs_elementwise(r, id_, tgt, val, vec):
+    g, tr = r.g, tgt["transform"]
+    params = r.params(tgt["dist"], tgt["params"])
+    xs, jacs = zip(*[r.const_x(tr, v, id_) for v in (val if vec else [val])])
+    elems, is_vec = r.elementwise(tgt["dist"], list(xs) if vec else xs[0], params)
+    if tr is not None:
+        elems = _plus(g, elems, list(jacs) if vec else jacs[0])
+    return elems, is_vec
+
+
+def _obs_term(r, id_, n):
+    """-> (term, datums) of an obs node (compiler.ex:272-336)."""
+    tgt = r.nodes[n["target"]]
+    if tgt["op"] != "rv":
+        # the reference gives such a node no term (compiler.ex:293); a det target that the
+        # lifting passes did not take is a model error here
+        raise CodegenError("obs %r does not target an rv (run the rewrite passes for det targets)" % id_)
+    val, meta = n["value"], n.get("meta") or dict(reduce="sum" if n["value"].ndim else None, censored=None)
+    cens = meta.get("censored")
+    tr = tgt["transform"]
+    if tr is not None and (cens == "interval" or tgt["dist"] in ("custom", "mv_normal", "gaussian_random_walk")):
+        raise CodegenError("obs %r: a transformed target with this distribution / censoring is not covered" % id_)
+    if tr is not None and cens:
+        # compiler.ex:274, 298-311 match the 3-tuple rv node only: on a target that carries a
+        # transform the 4-tuple clauses (:285, :325) run and the censoring is not applied
+        cens = None
+    vec = val.ndim > (1 if cens == "interval" else 0)
+    if tgt["dist"] == "custom":
+        elems, is_vec = _obs_custom(r, tgt, val, vec)
+    elif tgt["dist"] in VECTOR_DISTS:
+        elems, is_vec = _obs_vector_dist(r, id_, tgt, val, cens)
+    elif cens:
+        elems, is_vec = _obs_censored(r, id_, tgt, val, cens, vec)
+    else:
+        elems, is_vec = _obs_elementwise(r, id_, tgt, val, vec)
+    return _obs_meta(r.g, elems, is_vec, meta, id_)
+
+
+def _obs_meta(g, elems, is_vec, meta, id_):
+    """compiler.ex:401-418: weight, mask, reduce. -> (term, datums), datums = [(name, node)]: the
+    kept elements (id, i) of a summed vector term after the weight, else the one term as logp has
+    it -- none where a scalar mask switches it off."""
+    w = meta.get("weight")
+    if w is not None:
+        if is_vec:
+            elems = [g.mul(e, g.datum(float(w if w.ndim == 0 else w[i]))) for i, e in enumerate(elems)]
+        else:
+            if w.ndim != 0:
+                raise CodegenError("obs %r: a vector weight on a scalar term" % id_)
+            elems = g.mul(elems, g.datum(float(w)))
+    mk = meta.get("mask")
+    if mk is not None:
+        mk = np.asarray(mk)
+        if not is_vec:                        # Nx.select(mask, logp, 0.0) with a scalar mask
+            if mk.ndim != 0:
+                raise CodegenError("obs %r: a vector mask on a scalar term" % id_)
+            elems = elems if bool(mk) else g.lit(0.0)
+        else:
+            if mk.ndim != 1 or len(mk) != len(elems):
+                raise CodegenError("obs %r: mask does not match the term" % id_)
+            elems = [e if bool(mk[i]) else g.lit(0.0) for i, e in enumerate(elems)]
+    red = meta.get("reduce")
+    if not is_vec:
+        return elems, ([(id_, elems)] if mk is None or bool(mk) else [])
+    if red == "sum":                          # Nx.sum on the BinaryBackend: left to right
+        return _sum_left(g, elems), [((id_, i), e) for i, e in enumerate(elems) if mk is None or bool(mk[i])]
+    if red == "mean":
+        t = g.div(_sum_left(g, elems), g.lit(float(len(elems))))
+    elif red == "logsumexp":
+        t = _logsumexp(g, elems)
+    else:
+        raise CodegenError("obs %r: a vector-valued term needs a reduce" % id_)
+    return t, [(id_, t)]
+
+
+def _terms(r, ir):
+    """One term per free rv and per obs node, in Map.values order -> (terms, datums)."""
+    terms, datums = [], []
+    for id_ in _term_ids(ir, r.nodes):
+        n = r.nodes[id_]
+        if n["op"] == "det" or (n["op"] in ("obs", "meas_obs") and (n.get("meta") or {}).get("likelihood") is False):
+            continue                              # compiler.ex:268-269, 244-245: no term
+        if n["op"] == "rv":
+            if id_ in r.lay.offset:
+                terms.append(_rv_term(r, id_, n))
+        elif n["op"] == "meas_obs":
+            terms.append(_meas_obs_term(r, id_, n))
+        else:
+            t, dat = _obs_term(r, id_, n)
+            terms.append(t)
+            datums += dat
+    return terms, datums
+
+
+def _sum_logps(g, terms):
+    total = terms[0]                              # sum_logps, compiler.ex:394-395
+    for t in terms[1:]:
+        total = g.add(t, total)
+    if g.const[total]:
+        raise CodegenError("the log-density does not depend on the free variables")
+    return total
+
+
+# the sections of the header, each -> the header and the data array so far (+ what it generated)
+def _one_lane_section(g, total, d, one_lane):
+    """Value and gradient with the whole position in one lane's registers, where d allows it."""
+    if not one_lane:
+        return _emit_no_one_lane(d), np.zeros(0)
+    n_fwd = len(g.ops)
+    ad = _Grad(g, total)
+    ad.run(n_fwd)
+    grads = [ad.adj.get(g.key.get(("q", k))) for k in range(d)]
+    return _emit(g, total, grads, d), np.asarray(g.data, dtype=np.float64)
+
+
+def _plain_node(n, nodes):
+    if n["op"] == "rv":
+        return n["dist"] not in VECTOR_DISTS + ("custom", "mixture")
+    if n["op"] == "obs":
+        m = n.get("meta") or {}
+        return (m.get("reduce") in (None, "sum") and m.get("censored") is None and m.get("weight") is None
+                and m.get("mask") is None and nodes[n["target"]].get("transform") is None)
+    return False
+
+
+def _plate_section(ir, nodes, ncp, header, data):
+    """The 16-lane layout, when the model has plates to spread over lanes (codegen_vec.py): the
+    plug-in then carries Custom<16> next to Custom<1> and defaults to it."""
+    from . import codegen_vec
+    vec = codegen_vec.generate(ir, ncp=ncp) if all(_plain_node(n, nodes) for n in nodes.values()) else None
+    if vec is None:
+        return None, header, data
+    # (the plate layout's lane function is a section its users may include again, codegen_vec._emit)
+    return vec, "#ifndef EXMC_GEN_VEC_SECTION\n" + header + "\n" + vec["text"], np.concatenate([data, vec["vdata"]])
+
+
+def _lane_section(r, terms, d, lanes, waves_per_simd, scan, header, data):
+    """Several dimensions per lane (codegen_lanes.py): any d, the repeated terms over the lanes."""
+    from . import codegen_lanes
+    walks = codegen_lanes.find_chains(r.g, r.ncp_info, r.ncp_nodes) if scan else []
+    lay = codegen_lanes.generate(r.g, terms, r.custom_roots, d, lanes, waves_per_simd, walks)
+    # (the lane function is a section of its own that its users include once per table placement)
+    header = "#ifndef EXMC_GEN_LANES_SECTION\n" + header + \
+             "\n#define EXMC_GEN_LOFF %d   /* where the lane layout's table starts in data */\n" \
+             % data.size + lay["text"]
+    return lay, header, np.concatenate([data, lay["data"]])
+
+
+def _pointwise_section(g, datums, one_lane, group, header, data):
+    """The per-datum terms as a section of their own; a model without a one-lane form ships the
+    graph's data after the lane layout's table for it."""
+    doff = 0 if one_lane else int(data.size)
+    pw_data = np.zeros(0) if one_lane else np.asarray(g.data, dtype=np.float64)
+    header = "#ifndef EXMC_GEN_PW_SECTION\n" + header + _emit_pointwise(g, datums, doff, int(pw_data.size), group)
+    return header, np.concatenate([data, pw_data])
+
+
 def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, waves_per_simd=1, scan=True,
              pointwise=False, _pw_group=PW_GROUP):
     """Compiler.compile_for_sampling (compiler.ex:46-58) as source text. `rewrite_passes` runs the
@@ -932,390 +1385,37 @@ def generate(ir, ncp=True, vectorize=True, rewrite_passes=False, lanes=None, wav
     sorted-id order there too -- a reordering of the final sum (a few ulp of the log-density; the
     gradient's entries are sums over the same terms).
 
-    `pointwise`: keep the per-datum terms of the obs nodes (`apply_obs_meta`: what a datum is) and emit
+    `pointwise`: keep the per-datum terms of the obs nodes (`_obs_meta`: what a datum is) and emit
     them as a section of their own (`_emit_pointwise`); everything before that section is the text
     `pointwise=False` gives. `_pw_group`: datums per generated function; the results do not depend on it."""
+    from . import codegen_vec
     if rewrite_passes:
         ir = rewrite(ir)
     nodes, ncp_info = _apply_ncp(ir, ncp)
-    for id_, n in nodes.items():
-        if n["op"] == "obs" and n["target"] not in nodes:
-            raise CodegenError("obs %r targets unknown node %r" % (id_, n["target"]))
-    observed = _observed_targets(ir)
-    free = sorted(i for i, n in nodes.items() if n["op"] == "rv" and i not in observed)
-    if not free:
-        raise CodegenError("no free random variables")
-    # PointMap.build (point_map.ex:30-60): entries sorted by id, each `length` flat slots
-    offset, length, flat_names, vector_entries = {}, {}, [], {}
-    for id_ in free:
-        n = nodes[id_]
-        ln = _vector_length(id_, n) if n["dist"] in VECTOR_DISTS else 1
-        if n["dist"] in VECTOR_DISTS and n["transform"] is not None and n["dist"] != "dirichlet":
-            raise CodegenError("a transformed vector rv is not covered")
-        offset[id_], length[id_] = len(flat_names), ln
-        if n["dist"] in VECTOR_DISTS:
-            vector_entries[id_] = (len(flat_names), ln)
-            flat_names.extend("%s[%d]" % (id_, i) for i in range(ln))
-        else:
-            flat_names.append(id_)
-    if len(flat_names) > MAX_D_LANES:
-        raise CodegenError("%d free dimensions; the kernels take at most %d" % (len(flat_names), MAX_D_LANES))
-    if lanes is None and len(flat_names) > MAX_D:
-        lanes = 64 if len(flat_names) > 32 else 16
-    if lanes is not None and lanes not in (16, 32, 64):
-        raise CodegenError("lanes must be 16, 32 or 64")
-    one_lane = len(flat_names) <= MAX_D
-    g = _Graph()
-    custom_roots = set()      # terms that are the result of a Custom closure (a hand-written reduction)
-    ncp_nodes = {}            # non-centred id -> its node mu + sigma * z (the lane layout's scan chains)
-
-    def resolve_ref(id_, stack=()):
-        # compiler.ex:447-463
-        if id_ not in offset:
-            raise CodegenError("param ref %r is not a free random variable" % id_)
-        if id_ in stack:
-            raise CodegenError("cyclic non-centred reference through %r" % id_)
-        if id_ in vector_entries:
-            zs = [g.q(offset[id_] + i) for i in range(length[id_])]
-            return _stick_breaking_forward(g, zs) if nodes[id_]["dist"] == "dirichlet" else zs
-        z = g.q(offset[id_])
-        if id_ in ncp_info:
-            mu = resolve_value(ncp_info[id_]["mu"], stack + (id_,))
-            sigma = resolve_value(ncp_info[id_]["sigma"], stack + (id_,))
-            ncp_nodes[id_] = g.add(mu, g.mul(sigma, z))
-            return ncp_nodes[id_]
-        return _apply_transform(g, nodes[id_]["transform"], z)
-
-    def resolve_value(v, stack=()):
-        if isinstance(v, str) and v == "__obs_data":       # compiler.ex:114-118: the IR's data tensor
-            t = ir.data_tensor
-            if t is None:
-                raise CodegenError('"__obs_data" is referenced but the IR has no data (Builder.data)')
-            if t.ndim == 2:
-                return [[g.datum(float(x)) for x in row] for row in t]
-            return g.datum(float(t)) if t.ndim == 0 else [g.datum(float(x)) for x in t]
-        if isinstance(v, str):
-            return resolve_ref(v, stack)
-        if isinstance(v, F32):
-            return g.datum32(v)
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            return g.datum(float(a))
-        if a.ndim == 1:
-            return [g.datum(float(x)) for x in a]
-        raise CodegenError("params are scalars, vectors or refs")
-
-    def resolve_params(dist, params):
-        if dist == "mixture":     # nested: one params map per component, a weight vector
-            cps = [resolve_params(c, pp) for c, pp in zip(params.get("components", []), params.get("params", []))]
-            ws = resolve_value(params.get("weights"))
-            return dict(components=list(params.get("components", [])), params=cps,
-                        weights=ws if isinstance(ws, list) else [ws])
-        return {k: resolve_value(v) for k, v in params.items()}
-
-    def elementwise(dist, x, params):
-        if dist == "mixture":     # scalar params per component; only the value may be a vector
-            if isinstance(x, list):
-                return [_logpdf(g, dist, xi, params) for xi in x], True
-            return _logpdf(g, dist, x, params), False
-        n = max([len(v) for v in [x] + list(params.values()) if isinstance(v, list)] + [0])
-        if n == 0:
-            return _logpdf(g, dist, x, params), False
-        for v in [x] + list(params.values()):
-            if isinstance(v, list) and len(v) != n:
-                raise CodegenError("vector lengths differ")
-        pick = lambda v, i: v[i] if isinstance(v, list) else v   # noqa: E731
-        return [_logpdf(g, dist, pick(x, i), {k: pick(v, i) for k, v in params.items()})
-                for i in range(n)], True
-
-    ops = Ops(g)
-
-    def custom_logpdf(params, x):
-        fn = params.get("logpdf")
-        if not callable(fn):
-            raise CodegenError("a custom distribution needs a callable 'logpdf'")
-        rest = {k: resolve_value(v) for k, v in params.items() if k != "logpdf"}
-        t = fn(ops, x, rest)
-        if isinstance(t, list):
-            raise CodegenError("a custom logpdf must return a scalar (reduce inside the closure)")
-        custom_roots.add(t)
-        return t
-
-    def const_x(tr, v, id_):
-        # compiler.ex:284-291, 327-334, 350-357: z = inverse_transform(value), x = Transform.apply(z),
-        # the log-Jacobian at z joins the term (all constants of the data). v: a float or a node.
-        d = v if isinstance(v, int) else g.datum(float(v))
-        if tr is None:
-            return d, None
-        if tr == "log":
-            z = g.log(d)
-        elif tr == "softplus":
-            if isinstance(v, int):
-                raise CodegenError("%r: a softplus-transformed target of a computed value is not covered" % id_)
-            z = g.datum(math.log(math.expm1(float(v))))      # Nx.log(Nx.expm1(x)), host libm
-        elif tr == "logit":
-            z = g.sub(g.log(d), g.log1p(g.neg(d)))
-        else:
-            raise CodegenError("%r: an observation of a %r-transformed rv is not covered" % (id_, tr))
-        return _apply_transform(g, tr, z), _log_abs_det_jacobian(g, tr, z)
-
-    datums = []               # (name, node) of every datum, in term order then element index
-
-    def apply_obs_meta(elems, is_vec, meta, id_, pw=None):
-        # compiler.ex:401-418: weight, mask, reduce. pw: a list that takes the node's datums -- the
-        # kept elements (id, i) of a summed vector term after the weight (_obs_term says so: it is where
-        # the reduce is decided), else the one term as logp has it
-        t, per_element = _obs_term(elems, is_vec, meta, id_, pw)
-        if pw is not None and not per_element:
-            mk = meta.get("mask")
-            if is_vec or mk is None or bool(np.asarray(mk)):
-                pw.append((id_, t))
-        return t
-
-    def _obs_term(elems, is_vec, meta, id_, pw):
-        # -> the node's term, and whether its elements went to pw as datums of their own
-        w = meta.get("weight")
-        if w is not None:
-            if is_vec:
-                elems = [g.mul(e, g.datum(float(w if w.ndim == 0 else w[i]))) for i, e in enumerate(elems)]
-            else:
-                if w.ndim != 0:
-                    raise CodegenError("obs %r: a vector weight on a scalar term" % id_)
-                elems = g.mul(elems, g.datum(float(w)))
-        mk = meta.get("mask")
-        if mk is not None:
-            mk = np.asarray(mk)
-            if not is_vec:                        # Nx.select(mask, logp, 0.0) with a scalar mask
-                if mk.ndim != 0:
-                    raise CodegenError("obs %r: a vector mask on a scalar term" % id_)
-                elems = elems if bool(mk) else g.lit(0.0)
-            else:
-                if mk.ndim != 1 or len(mk) != len(elems):
-                    raise CodegenError("obs %r: mask does not match the term" % id_)
-                elems = [e if bool(mk[i]) else g.lit(0.0) for i, e in enumerate(elems)]
-        red = meta.get("reduce")
-        if not is_vec:
-            return elems, False
-        if red == "sum":
-            if pw is not None:
-                pw.extend(((id_, i), e) for i, e in enumerate(elems) if mk is None or bool(mk[i]))
-            return _sum_left(g, elems), True      # Nx.sum on the BinaryBackend: left to right
-        if red == "mean":
-            return g.div(_sum_left(g, elems), g.lit(float(len(elems)))), False
-        if red == "logsumexp":
-            return _logsumexp(g, elems), False
-        raise CodegenError("obs %r: a vector-valued term needs a reduce" % id_)
-
-    terms = []
-    term_order = getattr(ir, "term_order", None)
-    if term_order is not None and (sorted(term_order) != sorted(nodes) or len(term_order) != len(nodes)):
-        raise CodegenError("term_order does not match the node map")   # (a rewrite pass changed the key set)
-    if term_order is not None and len(nodes) <= MAX_NODES_SORTED and list(term_order) != sorted(nodes):
-        raise CodegenError("term_order of a map of <= %d keys must be the sorted ids (Erlang flatmaps "
-                           "are sorted)" % MAX_NODES_SORTED)
-    for id_ in (term_order if term_order is not None else sorted(nodes)):   # Map.values order, compiler.ex:176-180
-        n = nodes[id_]
-        if n["op"] == "det":                      # compiler.ex:268-269
-            continue
-        if n["op"] in ("obs", "meas_obs") and (n.get("meta") or {}).get("likelihood") is False:
-            continue                              # compiler.ex:244-245
-        if n["op"] == "rv":
-            if id_ not in offset:
-                continue
-            if n["dist"] in VECTOR_DISTS:
-                xs = [g.q(offset[id_] + i) for i in range(length[id_])]
-                if n["dist"] == "dirichlet":      # logpdf on the simplex + log|J| (compiler.ex:222-229)
-                    t = _logpdf_vector(g, "dirichlet", _stick_breaking_forward(g, xs), n["params"], resolve_value)
-                    terms.append(g.add(t, _stick_breaking_ladj(g, xs)))
-                    continue
-                terms.append(_logpdf_vector(g, n["dist"], xs, n["params"], resolve_value))
-                continue
-            z = g.q(offset[id_])
-            x = _apply_transform(g, n["transform"], z)
-            if n["dist"] == "custom":
-                t = custom_logpdf(n["params"], x)
-            else:
-                params = resolve_params(n["dist"], n["params"])
-                if n["dist"] != "mixture" and any(isinstance(v, list) for v in params.values()):
-                    raise CodegenError("free RV %r has a vector param" % id_)
-                t = _logpdf(g, n["dist"], x, params)
-            if n["transform"] is not None:
-                t = g.add(t, _log_abs_det_jacobian(g, n["transform"], z))   # compiler.ex:222-229
-            terms.append(t)
-        elif n["op"] == "meas_obs":
-            # compiler.ex:258-266, 342-369: eager -- the target's params are used as written (no
-            # refs), so the whole term is a constant of the data
-            tgt = nodes[n["target"]]
-            if tgt["op"] != "rv" or tgt["dist"] in VECTOR_DISTS + ("custom",):
-                raise CodegenError("meas_obs %r: target not covered" % id_)
-            if any(isinstance(v, str) for v in tgt["params"].values()):
-                raise CodegenError("meas_obs %r: the reference evaluates it eagerly, params must be constants" % id_)
-            params = resolve_params(tgt["dist"], tgt["params"])
-            val, info, tr = n["value"], n["info"], tgt["transform"]
-            if info[0] == "affine":
-                av, bv = np.asarray(info[1], dtype=np.float64), np.asarray(info[2], dtype=np.float64)
-                at = lambda c, i: g.datum(float(c if c.ndim == 0 else c[i]))   # noqa: E731
-                conv = lambda v, i: g.div(g.sub(g.datum(float(v)), at(bv, i)), at(av, i))   # noqa: E731
-                x = conv(val, 0) if val.ndim == 0 else [conv(v, i) for i, v in enumerate(val)]
-                if av.ndim == 0:
-                    jac = g.neg(g.log(g.abs(g.datum(float(av)))))
-                else:                             # -log|a| element by element: added to the vector term below
-                    jac = [g.neg(g.log(g.abs(g.datum(float(c))))) for c in av]
-            else:
-                sol = np.linalg.solve(info[1], val)                  # jit_solve: third-party LinAlg
-                x = [g.datum(float(v)) for v in sol]
-                jac = g.datum(-math.log(abs(float(np.linalg.det(info[1])))))
-            tjac = None
-            if tr is not None:                    # compiler.ex:350-359, 371-382: (logp + jac) + meas_jac
-                pairs = [const_x(tr, v, id_) for v in (x if isinstance(x, list) else [x])]
-                x = [p_[0] for p_ in pairs] if isinstance(x, list) else pairs[0][0]
-                tjac = [p_[1] for p_ in pairs]
-            t, vec = elementwise(tgt["dist"], x, params)
-            if vec:
-                # logpdf of a vector value is a vector; combined = logp + jac broadcasts, the meta's
-                # reduce (or, without one, sum_logps' Nx.sum, compiler.ex:396-397) folds it
-                if tjac is not None:
-                    t = [g.add(e, tjac[i if len(tjac) > 1 else 0]) for i, e in enumerate(t)]
-                t = [g.add(e, jac[i] if isinstance(jac, list) else jac) for i, e in enumerate(t)]
-            else:
-                if tjac is not None:
-                    t = g.add(t, tjac[0])
-                t = g.add(t, jac)
-            meta = dict(n.get("meta") or {})
-            if vec and meta.get("reduce") is None:
-                meta["reduce"] = "sum"
-            terms.append(apply_obs_meta(t, vec, meta, id_))       # (no datums: constants of the data)
-        else:
-            tgt = nodes[n["target"]]
-            if tgt["op"] != "rv":
-                # the reference gives such a node no term (compiler.ex:293); a det target that the
-                # lifting passes did not take is a model error here
-                raise CodegenError("obs %r does not target an rv (run the rewrite passes for det targets)" % id_)
-            val, meta = n["value"], n.get("meta") or dict(reduce="sum" if n["value"].ndim else None, censored=None)
-            cens = meta.get("censored")
-            tr = tgt["transform"]
-            if tr is not None and (cens == "interval" or tgt["dist"] in ("custom", "mv_normal", "gaussian_random_walk")):
-                raise CodegenError("obs %r: a transformed target with this distribution / censoring is not covered" % id_)
-            if tr is not None and cens:
-                # compiler.ex:274, 298-311 match the 3-tuple rv node only: on a target that carries a
-                # transform the 4-tuple clauses (:285, :325) run and the censoring is not applied
-                cens = None
-
-            vec = val.ndim > (1 if cens == "interval" else 0)
-            if tgt["dist"] == "custom":
-                x = [g.datum(float(v)) for v in val] if vec else g.datum(float(val))
-                t = custom_logpdf(tgt["params"], x)
-                elems, is_vec = t, False
-            elif tgt["dist"] in VECTOR_DISTS:
-                if val.ndim != 1 or cens:
-                    raise CodegenError("obs %r of a vector distribution needs a plain vector value" % id_)
-                xs, jac = [g.datum(float(v)) for v in val], None
-                if tr == "stick_breaking":        # compiler.ex:424: z from the datum, the point rebuilt from z
-                    zs = [g.datum(float(v)) for v in inverse_stick_breaking(val)]
-                    xs, jac = _stick_breaking_forward(g, zs), _stick_breaking_ladj(g, zs)
-                elif tr is not None:
-                    raise CodegenError("obs %r: transform %r on a vector distribution is not covered" % (id_, tr))
-                elems = _logpdf_vector(g, tgt["dist"], xs, tgt["params"], resolve_value)
-                if jac is not None:
-                    elems = g.add(elems, jac)
-                is_vec = False
-            elif cens:
-                params = resolve_params(tgt["dist"], tgt["params"])
-                if any(isinstance(v, list) for v in params.values()):
-                    raise CodegenError("censored obs %r: vector params are not covered" % id_)
-                rows = val if vec else val[None, ...]
-                out = []
-                for r in rows:
-                    value = (g.datum(float(r[0])), g.datum(float(r[1]))) if cens == "interval" else g.datum(float(r))
-                    out.append(_censored_loglik(g, cens, value, tgt["dist"], params))
-                elems, is_vec = (out, True) if vec else (out[0], False)
-            else:
-                params = resolve_params(tgt["dist"], tgt["params"])
-                if vec:
-                    xs, jacs = zip(*[const_x(tr, v, id_) for v in val])
-                    elems, is_vec = elementwise(tgt["dist"], list(xs), params)
-                    if tr is not None:
-                        elems = [g.add(e, j) for e, j in zip(elems, jacs)]
-                else:
-                    x, jac = const_x(tr, val, id_)
-                    elems, is_vec = elementwise(tgt["dist"], x, params)
-                    if tr is not None:
-                        elems = [g.add(e, jac) for e in elems] if is_vec else g.add(elems, jac)
-            t = apply_obs_meta(elems, is_vec, meta, id_, datums if pointwise else None)
-            terms.append(t)
+    lay = _layout(ir, nodes, lanes)
+    r = _Resolver(nodes, ir.data_tensor, lay, ncp_info)
+    terms, datums = _terms(r, ir)
     if pointwise and not datums:
         raise CodegenError("pointwise: the model has no datum (no obs node with a likelihood term)")
-    total = terms[0]                              # sum_logps, compiler.ex:394-395
-    for t in terms[1:]:
-        total = g.add(t, total)
-    if g.const[total]:
-        raise CodegenError("the log-density does not depend on the free variables")
-
-    out = Generated()
-    out.d = len(flat_names)
-    out.var_names = flat_names
-    out.vector_entries = vector_entries
-    # simplex entries: K - 1 flat slots each, a K-vector in the trace
-    out.simplex_entries = {i: vector_entries[i] for i in vector_entries if nodes[i]["dist"] == "dirichlet"}
-    out.transforms = {i: nodes[i]["transform"] for i in free if nodes[i]["transform"]}
-    out.ncp_info = ncp_info
-    out.lanes = 1
-    out.vec = out.lane_layout = None
-    if one_lane:
-        n_fwd = len(g.ops)
-        ad = _Grad(g, total)
-        ad.run(n_fwd)
-        grads = [ad.adj.get(g.key.get(("q", k))) for k in range(len(flat_names))]
-        out.data = np.asarray(g.data, dtype=np.float64)
-        out.header = _emit(g, total, grads, out.d)
-    else:
-        out.data = np.zeros(0)
-        out.header = _emit_no_one_lane(out.d)
-    # the 16-lane layout, when the model has plates to spread over lanes (codegen_vec.py): the
-    # plug-in then carries Custom<16> next to Custom<1> and defaults to it
-    from . import codegen_vec
-    def _plain_node(n):
-        if n["op"] == "rv":
-            return n["dist"] not in VECTOR_DISTS + ("custom", "mixture")
-        if n["op"] == "obs":
-            m = n.get("meta") or {}
-            return (m.get("reduce") in (None, "sum") and m.get("censored") is None and m.get("weight") is None
-                    and m.get("mask") is None and nodes[n["target"]].get("transform") is None)
-        return False
-    plain = all(_plain_node(n) for n in nodes.values())
-    if lanes is None and len(nodes) <= MAX_NODES_SORTED:
-        out.vec = codegen_vec.generate(ir, ncp=ncp) if (vectorize and plain) else None
-    if out.vec is not None:
-        # (the plate layout's lane function is a section its users may include again, codegen_vec._emit)
-        out.header = "#ifndef EXMC_GEN_VEC_SECTION\n" + out.header + "\n" + out.vec["text"]
-        out.data = np.concatenate([out.data, out.vec["vdata"]])
-        out.lanes = codegen_vec.G
-    if lanes is not None:
-        # several dimensions per lane (codegen_lanes.py): any d, the repeated terms over the lanes
-        from . import codegen_lanes
-        walks = codegen_lanes.find_chains(g, ncp_info, ncp_nodes) if scan else []
-        out.lane_layout = codegen_lanes.generate(g, terms, custom_roots, out.d, lanes, waves_per_simd, walks)
-        # (the lane function is a section of its own that its users include once per table placement)
-        out.header = "#ifndef EXMC_GEN_LANES_SECTION\n" + out.header + \
-                     "\n#define EXMC_GEN_LOFF %d   /* where the lane layout's table starts in data */\n" \
-                     % out.data.size + out.lane_layout["text"]
-        out.data = np.concatenate([out.data, out.lane_layout["data"]])
-        out.lanes = lanes
-    out.scan_chains = out.lane_layout["scan_chains"] if out.lane_layout is not None else []
-    out.datum_names, out.n_datums = None, -1
+    total = _sum_logps(r.g, terms)
+    d = len(lay.flat_names)
+    header, data = _one_lane_section(r.g, total, d, lay.one_lane)
+    vec = lane_layout = None
+    if vectorize and lay.lanes is None and len(nodes) <= MAX_NODES_SORTED:
+        vec, header, data = _plate_section(ir, nodes, ncp, header, data)
+    if lay.lanes is not None:
+        lane_layout, header, data = _lane_section(r, terms, d, lay.lanes, waves_per_simd, scan, header, data)
     if pointwise:
-        # the per-datum terms as a section of their own; a model without a one-lane form ships the
-        # graph's data after the lane layout's table for it
-        doff = 0 if one_lane else int(out.data.size)
-        pw_data = np.zeros(0) if one_lane else np.asarray(g.data, dtype=np.float64)
-        out.header = "#ifndef EXMC_GEN_PW_SECTION\n" + out.header + \
-                     _emit_pointwise(g, datums, doff, int(pw_data.size), int(_pw_group))
-        out.data = np.concatenate([out.data, pw_data])
-        out.datum_names = [nm for nm, _ in datums]
-        out.n_datums = len(datums)
-    out.digest = hashlib.sha256(out.header.encode()).hexdigest()[:16]
-    out.n_ops = out.header.count("\n")
-    return out
+        header, data = _pointwise_section(r.g, datums, lay.one_lane, int(_pw_group), header, data)
+    return Generated(
+        d=d, var_names=lay.flat_names, vector_entries=lay.vector_entries,
+        simplex_entries={i: e for i, e in lay.vector_entries.items() if nodes[i]["dist"] == "dirichlet"},
+        transforms={i: nodes[i]["transform"] for i in lay.free if nodes[i]["transform"]}, ncp_info=ncp_info,
+        lanes=lay.lanes if lay.lanes is not None else (codegen_vec.G if vec is not None else 1),
+        vec=vec, lane_layout=lane_layout, data=data, header=header,
+        scan_chains=lane_layout["scan_chains"] if lane_layout is not None else [],
+        datum_names=[nm for nm, _ in datums] if pointwise else None, n_datums=len(datums) if pointwise else -1,
+        digest=hashlib.sha256(header.encode()).hexdigest()[:16], n_ops=header.count("\n"))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1381,24 +1481,19 @@ def _emit_no_one_lane(d):
     return "\n".join(L) + "\n"
 
 
-def _emit(g, total, grads, d):
-    outputs = [total] + [x for x in grads if x is not None]
-    # liveness: everything reachable from the outputs
-    live = set(_reachable(outputs, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data", "q") else ()))
-    # folded constants: const non-literal nodes read by a dynamic node (or being an output)
+def _fold_slots(g, candidates):
+    """-> (slot, host). slot: the folded constants -- the constant non-literal nodes among
+    `candidates`, numbered in the order met; host: the nodes exmc_gen_fold needs to compute them."""
     slot = {}
-    for a in outputs:
+    for a in candidates:
         if g.const[a] and g.ops[a][0] != "lit" and a not in slot:
             slot[a] = len(slot)
-    for i in sorted(live):
-        if g.const[i]:
-            continue
-        for a in (g.ops[i][1:] if g.ops[i][0] != "q" else ()):
-            if g.const[a] and g.ops[a][0] != "lit" and a not in slot:
-                slot[a] = len(slot)
-    # host-side nodes needed for the slots
-    host = set(_reachable(slot, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data") else ()))
+    return slot, set(_reachable(slot, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data") else ()))
 
+
+def _ref_stmt(g, slot, q_text):
+    """-> (ref, stmt): node i as an operand, and the statement that computes it; dyn: in device code,
+    where a folded constant is read from c. q_text: the text of position entry j."""
     def ref(i, dyn):
         op = g.ops[i]
         if op[0] == "lit":
@@ -1408,44 +1503,44 @@ def _emit(g, total, grads, d):
         if op[0] == "data":
             return "data[%d]" % op[1]
         if op[0] == "q":
-            return "q[%d]" % op[1]
+            return q_text % op[1]
         return "t%d" % i
 
     def stmt(i, dyn):
-        op = g.ops[i]
-        a = [ref(x, dyn) for x in op[1:]] if op[0] not in ("lit", "data", "q") else []
-        return "  const double t%d = %s;" % (i, _expr_text(op[0], a))
+        return "  const double t%d = %s;" % (i, _expr_text(g.ops[i][0], [ref(x, dyn) for x in g.ops[i][1:]]))
+    return ref, stmt
 
-    L = []
-    L.append("/* generated by exmc_amd/codegen.py -- do not edit. Included twice over: by")
-    L.append(" * exmc_amd/csrc/exmc_models.hpp (device functor Custom<1>, -DEXMC_CUSTOM_HEADER) and by")
-    L.append(" * the host checker tests build from the same text. */")
-    L.append("#define EXMC_GEN_D %d" % d)
-    L.append("#define EXMC_GEN_ONE_LANE 1")
-    L.append("#define EXMC_GEN_NDATA %d" % len(g.data))
-    L.append("#define EXMC_GEN_NCONST %d" % max(1, len(slot)))
-    L.append("#define EXMC_GEN_LDS_LEVELS %d" % _lds_levels(d))
-    L.append("")
-    L.append("EXMC_GEN_HOST void exmc_gen_fold(const double* data, double* c) {")
-    for i in sorted(host):
-        if g.ops[i][0] not in ("lit", "data"):
-            L.append(stmt(i, False))
-    for i, k in sorted(slot.items(), key=lambda kv: kv[1]):
-        L.append("  c[%d] = %s;" % (k, ref(i, False)))
-    if not slot:
-        L.append("  c[0] = 0.0;")
-    L.append("  (void)data;")
-    L.append("}")
-    L.append("")
+
+def _fold_body(g, slot, host, ref, stmt):
+    """The lines of a fold function's body: the host-side nodes, then the slots."""
+    L = [stmt(i, False) for i in sorted(host) if g.ops[i][0] not in ("lit", "data")]
+    L += ["  c[%d] = %s;" % (k, ref(i, False)) for i, k in sorted(slot.items(), key=lambda kv: kv[1])]
+    return L + (["  c[0] = 0.0;"] if not slot else []) + ["  (void)data;", "}", ""]
+
+
+def _emit(g, total, grads, d):
+    outputs = [total] + [x for x in grads if x is not None]
+    # liveness: everything reachable from the outputs
+    live = sorted(_reachable(outputs, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data", "q") else ()))
+    dyn = [i for i in live if not g.const[i] and g.ops[i][0] != "q"]
+    # folded constants: const non-literal nodes read by a dynamic node (or being an output)
+    slot, host = _fold_slots(g, outputs + [a for i in dyn for a in g.ops[i][1:]])
+    ref, stmt = _ref_stmt(g, slot, "q[%d]")
+    L = ["/* generated by exmc_amd/codegen.py -- do not edit. Included twice over: by",
+         " * exmc_amd/csrc/exmc_models.hpp (device functor Custom<1>, -DEXMC_CUSTOM_HEADER) and by",
+         " * the host checker tests build from the same text. */",
+         "#define EXMC_GEN_D %d" % d,
+         "#define EXMC_GEN_ONE_LANE 1",
+         "#define EXMC_GEN_NDATA %d" % len(g.data),
+         "#define EXMC_GEN_NCONST %d" % max(1, len(slot)),
+         "#define EXMC_GEN_LDS_LEVELS %d" % _lds_levels(d),
+         "",
+         "EXMC_GEN_HOST void exmc_gen_fold(const double* data, double* c) {"]
+    L += _fold_body(g, slot, host, ref, stmt)
     L.append("EXMC_GEN_FN double exmc_gen_logp_grad(const double* c, const double* q, double* g) {")
-    for i in sorted(live):
-        if not g.const[i] and g.ops[i][0] != "q":
-            L.append(stmt(i, True))
-    for k, x in enumerate(grads):
-        L.append("  g[%d] = %s;" % (k, "0.0" if x is None else ref(x, True)))
-    L.append("  (void)c;")
-    L.append("  return %s;" % ref(total, True))
-    L.append("}")
+    L += [stmt(i, True) for i in dyn]
+    L += ["  g[%d] = %s;" % (k, "0.0" if x is None else ref(x, True)) for k, x in enumerate(grads)]
+    L += ["  (void)c;", "  return %s;" % ref(total, True), "}"]
     return "\n".join(L) + "\n"
 
 
@@ -1464,32 +1559,13 @@ def _emit_pointwise(g, datums, doff, ndata, group):
     if group < 1:
         raise CodegenError("pointwise: a generated function covers at least one datum")
     leaf = ("lit", "data", "q")
-    slot, bodies = {}, []
+    bodies = []               # (first datum, roots, everything live in the function) per function
     for k0 in range(0, len(datums), group):
         roots = [t for _, t in datums[k0:k0 + group]]
-        live = sorted(_reachable(roots, lambda i: () if g.const[i] or g.ops[i][0] in leaf else g.ops[i][1:]))
-        for i in live:
-            if g.const[i] and g.ops[i][0] != "lit" and i not in slot:
-                slot[i] = len(slot)
-        bodies.append((k0, roots, [i for i in live if not g.const[i] and g.ops[i][0] != "q"],
-                       sorted(g.ops[i][1] for i in live if g.ops[i][0] == "q")))
-    host = set(_reachable(slot, lambda i: g.ops[i][1:] if g.ops[i][0] not in ("lit", "data") else ()))
-
-    def ref(i, dyn):
-        op = g.ops[i]
-        if op[0] == "lit":
-            return _lit_text(op[1])
-        if dyn and i in slot:
-            return "c[%d]" % slot[i]
-        if op[0] == "data":
-            return "data[%d]" % op[1]
-        if op[0] == "q":
-            return "q%d" % op[1]
-        return "t%d" % i
-
-    def stmt(i, dyn):
-        return "  const double t%d = %s;" % (i, _expr_text(g.ops[i][0], [ref(x, dyn) for x in g.ops[i][1:]]))
-
+        bodies.append((k0, roots, sorted(_reachable(
+            roots, lambda i: () if g.const[i] or g.ops[i][0] in leaf else g.ops[i][1:]))))
+    slot, host = _fold_slots(g, [i for _, _, live in bodies for i in live])
+    ref, stmt = _ref_stmt(g, slot, "q%d")
     L = ["#if !defined(EXMC_GEN_VEC_SECTION) && !defined(EXMC_GEN_LANES_SECTION)",
          "/* per-datum log-likelihood terms (exmc_amd/codegen.py _emit_pointwise): %d datums in %d"
          " function%s */" % (len(datums), len(bodies), "" if len(bodies) == 1 else "s"),
@@ -1502,22 +1578,16 @@ def _emit_pointwise(g, datums, doff, ndata, group):
          "#else   /* EXMC_GEN_PW_SECTION: the functions themselves, included once */",
          "EXMC_GEN_HOST void exmc_gen_pw_fold(const double* data, double* c) {",
          "  data += EXMC_GEN_PW_DOFF;"]
-    for i in sorted(host):
-        if g.ops[i][0] not in ("lit", "data"):
-            L.append(stmt(i, False))
-    for i, k in sorted(slot.items(), key=lambda kv: kv[1]):
-        L.append("  c[%d] = %s;" % (k, ref(i, False)))
-    if not slot:
-        L.append("  c[0] = 0.0;")
-    L += ["  (void)data;", "}", ""]
-    for n, (k0, roots, dyn, qs) in enumerate(bodies):
+    L += _fold_body(g, slot, host, ref, stmt)
+    for n, (k0, roots, live) in enumerate(bodies):
         L.append("EXMC_GEN_PW_FN void exmc_gen_pw_%d(const double* c, int i0, int i1 EXMC_GEN_PW_DECL) {" % n)
-        L.extend("  const double q%d = EXMC_GEN_PW_Q(%d);" % (j, j) for j in qs)   # each entry read once
-        L.extend(stmt(i, True) for i in dyn)
+        L.extend("  const double q%d = EXMC_GEN_PW_Q(%d);" % (j, j)     # each entry read once
+                 for j in sorted(g.ops[i][1] for i in live if g.ops[i][0] == "q"))
+        L.extend(stmt(i, True) for i in live if not g.const[i] and g.ops[i][0] != "q")
         L.extend("  EXMC_GEN_PW_OUT(%d, %s);" % (k0 + j, ref(t, True)) for j, t in enumerate(roots))
         L += ["  (void)c; (void)i0; (void)i1;", "}", ""]
     L.append("EXMC_GEN_FN void exmc_gen_pw_eval(const double* c, int i0, int i1 EXMC_GEN_PW_DECL) {")
-    for n, (k0, roots, _, _) in enumerate(bodies):
+    for n, (k0, roots, _) in enumerate(bodies):
         L.append("  if (i0 < %d && i1 > %d) exmc_gen_pw_%d(c, i0, i1 EXMC_GEN_PW_PASS);" % (k0 + len(roots), k0, n))
     L += ["}", "#endif   /* EXMC_GEN_PW_SECTION */"]
     return "\n".join(L) + "\n"

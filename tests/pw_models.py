@@ -148,3 +148,39 @@ def two_obs_ir(with_a=True):
         ir.obs("y_a", "y", [0.3, -1.2, 2.2, 0.9, 1.4, -0.1, 0.7], weight=[1.0, 0.5, 2.0, 1.0, 0.25, 3.0, 1.5])
     ir.obs("y_b", "y", [1.1, 0.2, -0.4, 0.6, 1.9])
     return ir
+
+
+def meta_ir():
+    """every kind of obs node next to each other: what counts as a datum"""
+    ir = cg.IR()
+    ir.rv("m", "normal", dict(mu=0.0, sigma=2.0))
+    ir.rv("s", "half_normal", dict(sigma=1.5), transform="log")
+    ir.rv("x_rv", "normal", dict(mu="m", sigma="s"))
+    ir.obs("a_w", "x_rv", [0.1, 0.2, 0.3], weight=[1.0, 0.5, 2.0])
+    ir.obs("b_mask", "x_rv", [0.1, 0.2, 0.3, 0.4, 0.5], mask=[True, False, True, False, True], weight=2.0)
+    ir.obs("c_mean", "x_rv", [0.5, 0.6], reduce="mean")
+    ir.obs("d_lse", "x_rv", [0.5, 0.6, 0.7], reduce="logsumexp")
+    ir.obs("e_off", "x_rv", [0.5, 0.6], likelihood=False)
+    ir.rv("k_rv", "normal", dict(mu=1.0, sigma=2.0))
+    ir.meas_obs("f_meas", "k_rv", 3.0, ("affine", 2.0, 1.0))
+    ir.obs("g_left", "x_rv", [-0.5, 0.2], censored="left")
+    ir.obs("h_right", "x_rv", 1.7, censored="right")
+    ir.obs("i_int", "x_rv", dict(lower=[-1.0, 0.0], upper=[0.5, 2.0]), censored="interval")
+    ir.obs("j_masked_scalar", "x_rv", 0.3, mask=False)
+
+    def lik(o, x, p):
+        return o.sum([o.logpdf("normal", xj, dict(mu=p["m"], sigma=o.lit(1.0))) for xj in x])
+    ir.rv("z_rv", "custom", dict(logpdf=lik, m="m"))
+    ir.obs("k_custom", "z_rv", [0.4, -1.1, 2.0])
+    ir.rv("mv_rv", "mv_normal", dict(mu=[0.1, -0.2], cov=[[1.0, 0.3], [0.3, 2.0]]))
+    ir.obs("l_mv", "mv_rv", [0.3, 0.4])
+    return ir
+
+
+def no_datum_ir():
+    """the only obs node has likelihood: false"""
+    ir = cg.IR()
+    ir.rv("mu", "normal", dict(mu=0.0, sigma=1.0))
+    ir.rv("x", "normal", dict(mu="mu", sigma=1.0))
+    ir.obs("x_obs", "x", 0.5, likelihood=False)
+    return ir

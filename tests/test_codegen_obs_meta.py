@@ -77,23 +77,15 @@ def test_reference_erfc_polynomial_is_what_is_generated():
     for x in np.linspace(-3, 3, 25):
         assert abs(_erfc_as(x) - special.erfc(x)) < 2e-7
     # a single right-censored Normal obs: log(1 - Phi((x - mu) / sigma)) with that erfc
-    ir = cg.IR()
-    ir.rv("mu", "normal", dict(mu=0.0, sigma=10.0))
-    ir.rv("x_rv", "normal", dict(mu="mu", sigma=2.0))
-    ir.obs("x", "x_rv", 1.0, censored="right")
-    gen = cg.generate(ir)
+    gen = cg.generate(GM.right_censored_normal_ir())
     lp = GC.logp_grad(gen, np.array([0.3]))[0]
     want = stats.norm.logpdf(0.3, 0.0, 10.0) + math.log(_cdf(-(1.0 - 0.3) / 2.0))
     assert abs(lp - want) < 1e-6 and abs(lp - (stats.norm.logpdf(0.3, 0.0, 10.0) + stats.norm.logsf(1.0, 0.3, 2.0))) < 1e-6
 
 
 def test_refusals():
-    ir = cg.IR()
-    ir.rv("a", "gamma", dict(alpha=2.0, beta=1.0), transform="log")
-    ir.rv("x_rv", "gamma", dict(alpha="a", beta=1.0))
-    ir.obs("x", "x_rv", 1.0, censored="right")                 # censored.ex has no Gamma clause
     with pytest.raises(cg.CodegenError):
-        cg.generate(ir)
+        cg.generate(GM.censored_gamma_ir())
     with pytest.raises(cg.CodegenError):
         cg.IR().rv("x", "normal", dict(mu=0.0, sigma=1.0)).obs("o", "x", [1.0, 2.0], mask=[True])
     with pytest.raises(cg.CodegenError):

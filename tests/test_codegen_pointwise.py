@@ -60,34 +60,8 @@ def test_scalar_and_vector_obs_names():
     assert _names(cg.simple_ir([1.0, 2.0, 3.0])) == [("y_obs", 0), ("y_obs", 1), ("y_obs", 2)]
 
 
-def _meta_ir():
-    ir = cg.IR()
-    ir.rv("m", "normal", dict(mu=0.0, sigma=2.0))
-    ir.rv("s", "half_normal", dict(sigma=1.5), transform="log")
-    ir.rv("x_rv", "normal", dict(mu="m", sigma="s"))
-    ir.obs("a_w", "x_rv", [0.1, 0.2, 0.3], weight=[1.0, 0.5, 2.0])
-    ir.obs("b_mask", "x_rv", [0.1, 0.2, 0.3, 0.4, 0.5], mask=[True, False, True, False, True], weight=2.0)
-    ir.obs("c_mean", "x_rv", [0.5, 0.6], reduce="mean")
-    ir.obs("d_lse", "x_rv", [0.5, 0.6, 0.7], reduce="logsumexp")
-    ir.obs("e_off", "x_rv", [0.5, 0.6], likelihood=False)
-    ir.rv("k_rv", "normal", dict(mu=1.0, sigma=2.0))
-    ir.meas_obs("f_meas", "k_rv", 3.0, ("affine", 2.0, 1.0))
-    ir.obs("g_left", "x_rv", [-0.5, 0.2], censored="left")
-    ir.obs("h_right", "x_rv", 1.7, censored="right")
-    ir.obs("i_int", "x_rv", dict(lower=[-1.0, 0.0], upper=[0.5, 2.0]), censored="interval")
-    ir.obs("j_masked_scalar", "x_rv", 0.3, mask=False)
-
-    def lik(o, x, p):
-        return o.sum([o.logpdf("normal", xj, dict(mu=p["m"], sigma=o.lit(1.0))) for xj in x])
-    ir.rv("z_rv", "custom", dict(logpdf=lik, m="m"))
-    ir.obs("k_custom", "z_rv", [0.4, -1.1, 2.0])
-    ir.rv("mv_rv", "mv_normal", dict(mu=[0.1, -0.2], cov=[[1.0, 0.3], [0.3, 2.0]]))
-    ir.obs("l_mv", "mv_rv", [0.3, 0.4])
-    return ir
-
-
 def test_what_counts_as_a_datum():
-    assert _names(_meta_ir()) == [
+    assert _names(PM.meta_ir()) == [
         ("a_w", 0), ("a_w", 1), ("a_w", 2),
         ("b_mask", 0), ("b_mask", 2), ("b_mask", 4),          # switched-off elements dropped, indices kept
         "c_mean", "d_lse",                                     # one datum each; e_off, f_meas: none
@@ -96,7 +70,7 @@ def test_what_counts_as_a_datum():
 
 
 def test_weight_and_mask_are_in_the_datum_and_reductions_are_the_logp_term():
-    gen = cg.generate(_meta_ir(), pointwise=True)
+    gen = cg.generate(PM.meta_ir(), pointwise=True)
     q = _q(gen.d, n=5)
     t = PC.terms(gen, q)
     nm = gen.datum_names
@@ -122,10 +96,7 @@ def test_term_order_of_more_than_32_nodes_is_followed():
 
 
 def test_a_model_without_a_datum_raises():
-    ir = cg.IR()
-    ir.rv("mu", "normal", dict(mu=0.0, sigma=1.0))
-    ir.rv("x", "normal", dict(mu="mu", sigma=1.0))
-    ir.obs("x_obs", "x", 0.5, likelihood=False)
+    ir = PM.no_datum_ir()
     cg.generate(ir)
     with pytest.raises(cg.CodegenError, match="no datum"):
         cg.generate(ir, pointwise=True)

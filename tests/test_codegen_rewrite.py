@@ -10,6 +10,7 @@ import pytest
 from scipy import stats
 
 import gen_checker as GC
+import gen_models as GM
 from exmc_amd import codegen as cg
 
 
@@ -41,11 +42,7 @@ def test_exponential_poisson_model_of_the_reference_tests():
     # test/new_dist_test.exs:270-290: mu ~ Exponential(0.1), y ~ Poisson(mu), ten counts; the model is
     # written without transforms there. The passes give mu :log, and y -- observed -- :log as well, so
     # the obs term is evaluated at exp(log y) and log y joins it (compiler.ex:325-334).
-    data = [2.0, 4.0, 3.0, 1.0, 5.0, 3.0, 2.0, 4.0, 3.0, 3.0]
-    ir = cg.IR()
-    ir.rv("mu", "exponential", {"lambda": 0.1})
-    ir.rv("y", "poisson", dict(mu="mu"))
-    ir.obs("y_obs", "y", data)
+    data, ir = GM.POISSON_DATA, GM.poisson_ir()
     gen = cg.generate(ir, rewrite_passes=True)
     assert gen.transforms == {"mu": "log"} and gen.d == 1
     for z in (-1.0, 0.3, 1.1, 2.0):
@@ -62,24 +59,8 @@ def test_exponential_poisson_model_of_the_reference_tests():
 
 
 def test_lifted_det_obs_equals_the_meas_obs_spelling():
-    def base():
-        ir = cg.IR()
-        ir.rv("m", "normal", dict(mu=0.0, sigma=2.0))
-        ir.rv("x", "normal", dict(mu=1.0, sigma=0.5))
-        ir.rv("lik_rv", "normal", dict(mu="m", sigma=1.0))
-        ir.obs("lik", "lik_rv", [0.3, -0.2])
-        ir.rv("v", "normal", dict(mu=0.0, sigma=1.5))
-        return ir
-    a_mat = [[2.0, 0.5], [0.0, 1.5]]
-    w = [1.0, 0.25, 3.0]
-    lifted = base()
-    lifted.det("ax", "affine", [2.0, -1.0, "x"])
-    lifted.obs("ax_obs", "ax", [0.5, 1.5, 2.5], weight=w)
-    lifted.det("mv", "matmul", [a_mat, "v"])
-    lifted.obs("mv_obs", "mv", [0.7, -0.4])
-    direct = base()
-    direct.meas_obs("ax_obs", "x", [0.5, 1.5, 2.5], ("affine", 2.0, -1.0), meta=dict(weight=np.asarray(w), reduce="sum"))
-    direct.meas_obs("mv_obs", "v", [0.7, -0.4], ("matmul", a_mat))
+    a_mat, w = GM.LIFT_A, GM.LIFT_W
+    lifted, direct = GM.lifted_ir(), GM.lifted_direct_ir()
     ga, gb = cg.generate(lifted, rewrite_passes=True), cg.generate(direct)
     assert ga.var_names == gb.var_names == ["m"]
     q = [0.4]
@@ -97,15 +78,7 @@ def test_lifted_det_obs_equals_the_meas_obs_spelling():
 
 def test_meas_obs_of_a_transformed_target_and_likelihood_false():
     # compiler.ex:371-382: x = (y - b) / a, z = log x, the term is logpdf(exp z) + z - log|a|
-    ir = cg.IR()
-    ir.rv("m", "normal", dict(mu=0.0, sigma=1.0))
-    ir.rv("lik_rv", "normal", dict(mu="m", sigma=1.0))
-    ir.obs("lik", "lik_rv", 0.2)
-    ir.rv("r", "gamma", dict(alpha=2.0, beta=1.5), transform="log")
-    ir.meas_obs("r_obs", "r", [3.0, 5.0], ("affine", 2.0, 1.0))
-    ir.rv("off_rv", "normal", dict(mu="m", sigma=0.1))
-    ir.obs("off", "off_rv", [9.0, 9.0], likelihood=False)
-    gen = cg.generate(ir)
+    gen = cg.generate(GM.meas_transformed_ir())
     lp = _lp(gen, [0.1])[0]
     xs = np.array([1.0, 2.0])
     want = (stats.norm.logpdf(0.1) + stats.norm.logpdf(0.2, 0.1, 1.0)
@@ -118,31 +91,18 @@ def test_censoring_is_not_applied_to_a_target_that_carries_a_transform():
     # compiler.ex:274 and :298-311 match {:rv, dist, params} only; a Weibull target written without
     # a transform gets :log from the first pass and lands in the 4-tuple clause (:325-334)
     def model(**opts):
-        ir = cg.IR()
-        ir.rv("k", "gamma", dict(alpha=2.0, beta=1.0))
-        ir.rv("t_rv", "weibull", {"k": "k", "lambda": 2.0})
-        ir.obs("t", "t_rv", [1.0, 2.5], **opts)
-        return cg.generate(ir, rewrite_passes=True)
+        return cg.generate(GM.weibull_ir(**opts), rewrite_passes=True)
     a, b = model(censored="right"), model()
     assert _lp(a, [0.2])[0] == _lp(b, [0.2])[0]
     # an explicit "no transform" target keeps the survival term
-    ir = cg.IR()
-    ir.rv("k", "gamma", dict(alpha=2.0, beta=1.0), transform="log")
-    ir.rv("t_rv", "weibull", {"k": "k", "lambda": 2.0})
-    ir.obs("t", "t_rv", [1.0, 2.5], censored="right")
+    ir = GM.weibull_ir("log", censored="right")
     k = math.exp(0.2)
     want = stats.gamma.logpdf(k, 2.0) + 0.2 + np.sum(stats.weibull_min.logsf([1.0, 2.5], k, scale=2.0))
     assert abs(_lp(cg.generate(ir), [0.2])[0] - want) <= 2e-5 * (1 + abs(want))
 
 
 def test_dirichlet_observation_on_its_default_transform():
-    ir = cg.IR()
-    ir.rv("a", "gamma", dict(alpha=2.0, beta=1.0))
-    ir.rv("th", "dirichlet", dict(alpha=[2.0, 3.0, 1.5]))
-    ir.obs("th_obs", "th", [0.2, 0.5, 0.3])
-    ir.rv("y_rv", "normal", dict(mu="a", sigma=1.0))
-    ir.obs("y", "y_rv", 1.0)
-    gen = cg.generate(ir, rewrite_passes=True)
+    gen = cg.generate(GM.dirichlet_obs_ir(), rewrite_passes=True)
     x = np.array([0.2, 0.5, 0.3])
     z = cg.inverse_stick_breaking(x)
     h = 1e-6
@@ -160,16 +120,7 @@ def test_builder_data_resolves_obs_data_refs():
     (compiler.ex:103-118): the tensor reaches the closure as constants of the data array, so two
     data sets of one shape share the generated text."""
     def model(y):
-        def logpdf(o, x, p):           # sum_i N(y_i | x, sigma) over the data tensor, up to its constant
-            terms = []
-            for yi in p["y"]:
-                z = o.div(o.sub(yi, x), p["sigma"])
-                terms.append(o.mul(o.lit(-0.5), o.mul(z, z)))
-            return o.sub(o.sum(terms), o.mul(o.lit(float(len(p["y"]))), o.log(p["sigma"])))
-        ir = cg.IR().data(y)
-        ir.rv("sigma", "half_cauchy", dict(scale=2.0), transform="log")
-        ir.rv("m", "custom", dict(logpdf=logpdf, y="__obs_data", sigma="sigma"))
-        return cg.generate(ir)
+        return cg.generate(GM.data_ir(y))
     y1, y2 = np.array([0.3, -1.2, 2.2, 0.9]), np.array([5.0, 4.0, 6.5, 5.5])
     g1, g2 = model(y1), model(y2)
     assert g1.header == g2.header and not np.array_equal(g1.data, g2.data)
@@ -182,12 +133,9 @@ def test_builder_data_resolves_obs_data_refs():
         assert abs(lp - want) <= 2e-6 * (1 + abs(want))
         assert abs(grad[0] - np.sum((y - q[0]) / sg ** 2)) <= 1e-9 * (1 + abs(grad[0]))
     with pytest.raises(cg.CodegenError):
-        ir = cg.IR()
-        ir.rv("m", "custom", dict(logpdf=lambda o, x, p: x, y="__obs_data"))
-        cg.generate(ir)
+        cg.generate(GM.data_missing_ir())
     # a matrix arrives as rows
-    ir = cg.IR().data([[1.0, 2.0], [3.0, 4.0]])
-    ir.rv("m", "custom", dict(logpdf=lambda o, x, p: o.mul(o.neg(o.mul(x, x)), p["a"][1][0]), a="__obs_data"))
+    ir = GM.data_matrix_ir()
     assert abs(_lp(cg.generate(ir), [0.5])[0] + 0.75) < 1e-15
 
 

@@ -28,9 +28,7 @@ def test_doctest_literals():
     assert abs(_one("beta", dict(alpha=2.0, beta=3.0), 0.4, "logit", logit) - math.log(0.4 * 0.6) - 0.546966) < 3e-6
     assert round(_one("weibull", {"k": 2.0, "lambda": 1.0}, 1.0, "log", math.log), 6) == -0.306853        # weibull.ex:9-10
     assert abs(_one("uniform01", {}, 0.3, "logit", logit) - math.log(0.3 * 0.7)) < 1e-12                 # uniform01.ex:8-9: 0.0
-    ir = cg.IR()
-    ir.rv("th", "dirichlet", dict(alpha=[1.0, 1.0, 1.0]), transform="stick_breaking")
-    gen = cg.generate(ir)
+    gen = cg.generate(GM.free_dirichlet_ir((1.0, 1.0, 1.0), "stick_breaking"))
     assert gen.d == 2 and gen.var_names == ["th[0]", "th[1]"] and gen.simplex_entries == {"th": (0, 2)}
     z = cg.inverse_stick_breaking([1 / 3, 1 / 3, 1 / 3])
     np.testing.assert_allclose(cg.stick_breaking(z), [1 / 3] * 3, atol=1e-15)
@@ -105,14 +103,10 @@ def test_simplex_init_and_trace():
 
 
 def test_refusals():
-    ir = cg.IR()
-    ir.rv("th", "dirichlet", dict(alpha=[1.0, 1.0, 1.0]))                  # a free simplex rv needs its transform
     with pytest.raises(cg.CodegenError):
-        cg.generate(ir)
-    ir = cg.IR()
-    ir.rv("th", "dirichlet", dict(alpha=[1.0]), transform="stick_breaking")
+        cg.generate(GM.free_dirichlet_ir())                                  # a free simplex rv needs its transform
     with pytest.raises(cg.CodegenError):
-        cg.generate(ir)
+        cg.generate(GM.free_dirichlet_ir((1.0,), "stick_breaking"))
     ir = cg.IR()
     ir.rv("x", "inverse_gamma", dict(alpha=2.0, beta=1.0), transform="log")   # not one of lib/exmc/dist
     with pytest.raises(cg.CodegenError):

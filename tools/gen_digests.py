@@ -85,6 +85,21 @@ def cases():
     add("term_order/sorted", lambda: term_order_ir()[0], ncp=False)
     add("term_order/reversed", lambda: term_order_ir()[0].order(list(reversed(ids))), ncp=False)
     add("term_order/reversed/lanes=16", lambda: term_order_ir()[0].order(list(reversed(ids))), ncp=False, lanes=16)
+    # the per-datum section: one-lane models, one that has the lane layout only (its section ships its own
+    # data), every kind of obs node, group sizes that do and do not divide the datum count, the refusals
+    import pw_models as PM
+    for name, fn in (("simple", cg.simple_ir), ("eight_schools", cg.eight_schools_ir), ("walk24_lanes", lambda: PM.walk_ir(22)),
+                     ("walk8", lambda: PM.walk_ir(6)), ("meta", PM.meta_ir), ("counts", PM.counts_ir), ("long", PM.long_ir),
+                     ("two_obs", PM.two_obs_ir), ("survival", GM.survival_ir), ("no_datum", PM.no_datum_ir),
+                     ("literal_custom", lambda: GM.literal_custom_ir(observed=True))):
+        add("pointwise/%s" % name, fn, pointwise=True)
+    for group in (0, 1, 3, 1000):
+        add("pointwise/counts/group=%d" % group, PM.counts_ir, pointwise=True, _pw_group=group)
+    add("pointwise/walk24_lanes/lanes=64", lambda: PM.walk_ir(22), pointwise=True, lanes=64)
+    add("pointwise/simple/lanes=16", cg.simple_ir, pointwise=True, lanes=16)
+    # one small model per remaining branch of the term walk, the refusals with their messages
+    for name, fn, kw in GM.corner_cases():
+        add("corner/%s" % name, fn, **kw)
     return out
 
 
