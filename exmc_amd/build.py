@@ -29,6 +29,7 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_pathfinder.hpp"),
     os.path.join(HERE, "csrc", "exmc_advi.hpp"),
     os.path.join(HERE, "csrc", "exmc_predictive.hpp"),
+    os.path.join(HERE, "csrc", "exmc_ppc.hpp"),
     os.path.join(HERE, "csrc", "exmc_plugin_part.hip"),
     COMMON_SRC,
     os.path.join(HERE, "csrc", "exmc_plugin_kernels.inc"),
@@ -40,6 +41,7 @@ DEPS = [
     os.path.join(ROOT, "include", "exmc_hip_pathfinder.h"),
     os.path.join(ROOT, "include", "exmc_hip_advi.h"),
     os.path.join(ROOT, "include", "exmc_hip_predictive.h"),
+    os.path.join(ROOT, "include", "exmc_hip_ppc.h"),
     os.path.join(ROOT, "include", "exmc_detmath.h"),
     os.path.join(ROOT, "include", "exmc_logtab.h"),
     os.path.join(ROOT, "include", "exmc_zig_tables.h"),

@@ -12,6 +12,7 @@
 #include "../../include/exmc_hip_pathfinder.h"
 #include "../../include/exmc_hip_advi.h"
 #include "../../include/exmc_hip_predictive.h"
+#include "../../include/exmc_hip_ppc.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2178,6 +2179,58 @@ int predictive_launch(exmc_hip_model* m, const Src& src, const PredictiveParams&
   return finish_timing(m);   // waits for the kernel: before the source's data image is freed
 }
 
+// the observed values of the kind's datums in the handle's order (ppc_obs_kernel), on the host
+template <class Src>
+int ppc_observed(exmc_hip_model* m, const Src& src, int N, double* y) {
+  CallBuf dy;
+  int rc = dy.alloc((size_t)N * 8);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ppc_obs_kernel<Src>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, m->stream, src, N,
+                     dy.as<double>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(y, dy.p, (size_t)N * 8, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return EXMC_OK;
+}
+
+// the four statistics of one data set v [N] about the observed mean m0 (include/exmc_hip_ppc.h): the
+// expressions ppc_kernel applies to every replicated data set, here for the observed one
+void ppc_tstat(const double* v, int N, double m0, double* T) {
+  const double Nd = (double)N;
+  double A = 0.0, Bq = 0.0, mn = INFINITY, mx = -INFINITY;
+  for (int i = 0; i < N; i++) {
+    const double e = v[i] - m0;
+    A = A + e;
+    Bq = Bq + e * e;
+    mn = (v[i] < mn) ? v[i] : mn;
+    mx = (v[i] > mx) ? v[i] : mx;
+  }
+  T[0] = m0 + A / Nd;
+  T[1] = (Bq - (A * A) / Nd) / (Nd - 1.0);
+  T[2] = mn;
+  T[3] = mx;
+}
+
+// posterior predictive checks (ppc_kernel, exmc_ppc.hpp): the observed values and their statistics first,
+// then one wavefront per 64 chains between the handle's events
+template <class Src>
+int ppc_launch(exmc_hip_model* m, const Src& src, PpcParams& P, double* y) {
+  int rc = ppc_observed(m, src, P.N, y);
+  if (rc) return rc;
+  double sum = 0.0;
+  for (int i = 0; i < P.N; i++) sum = sum + y[i];
+  P.m0 = sum / (double)P.N;
+  ppc_tstat(y, P.N, P.m0, P.t_obs);
+  const size_t lds = ppc_lds_bytes(m->d);
+  if (lds > 64 * 1024) EXMC_KMAXLDS(ppc_kernel<Src>, lds);
+  const unsigned blocks = (unsigned)((P.C + kPpBlock - 1) / kPpBlock);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  hipLaunchKernelGGL(ppc_kernel<Src>, dim3(blocks), dim3(kPpBlock), lds, m->stream, src, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the kernel: before the source's data image is freed
+}
+
 #endif
 
 #ifdef EXMC_GEN_POINTWISE
@@ -2594,6 +2647,123 @@ int exmc_hip_posterior_predictive_host(exmc_hip_model* m, exmc_hip_predictive_op
   HIP_TRY(hipMemcpy(h.data(), d_yrep, h.size() * 8, hipMemcpyDeviceToHost));
   transpose_trace_vec(h.data(), yrep, n_draws, (int)N, n_chains);
   if (rng_state) HIP_TRY(hipMemcpy(rng_state, d_rng, 2 * C * 8, hipMemcpyDeviceToHost));
+#endif
+  return rc;
+}
+
+// ---- posterior predictive checks (include/exmc_hip_ppc.h; ppc_kernel, exmc_ppc.hpp) -------------------
+static int ppc_check(exmc_hip_model* m, const exmc_hip_predictive_opts& o, const void* draws, int n_draws, int d,
+                     int n_chains, bool outputs) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)o; (void)draws; (void)n_draws; (void)d; (void)n_chains; (void)outputs;
+  return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive checks: generated models are not supported");
+#else
+  if (m->kind == EXMC_MODEL_CUSTOM || ic_n_data(m) < 0)
+    return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive checks: this model kind has no built-in datums");
+  if (!draws || !outputs || d != m->d || n_draws < 1 || n_chains < 1 || o.chain_lo < 0 || o.resume)
+    return fail(EXMC_ERR_BADARG, "posterior predictive checks: bad arguments");
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_ppc(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws_dev, int n_draws, int d,
+                 int n_chains, double* datum_sums_dev, int64_t* datum_counts_dev, int32_t* chain_counts_dev,
+                 double* tstat_dev, double* t_obs, double* m0, double* y_obs) {
+  int rc = ppc_check(m, o, draws_dev, n_draws, d, n_chains,
+                     datum_sums_dev && datum_counts_dev && chain_counts_dev && t_obs && m0);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)tstat_dev; (void)y_obs;
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  PpcParams P;
+  P.draws = draws_dev;
+  P.datum_sums = datum_sums_dev;
+  P.datum_counts = (long long*)datum_counts_dev;
+  P.chain_counts = (int*)chain_counts_dev;
+  P.tstat = tstat_dev;
+  P.S = n_draws;
+  P.d = d;
+  P.C = n_chains;
+  P.N = ic_n_data(m);
+  P.chain_lo = o.chain_lo;
+  P.base_seed = o.seed;
+  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
+  P.nor_r = EXMC_NOR_R;
+  std::vector<double> y((size_t)P.N);
+  rc = ic_with_src(m, [&](const auto& src) { return ppc_launch(m, src, P, y.data()); });
+  if (rc) return rc;
+  for (int k = 0; k < kPpcStats; k++) t_obs[k] = P.t_obs[k];
+  *m0 = P.m0;
+  if (y_obs) std::copy(y.begin(), y.end(), y_obs);
+#endif
+  return rc;
+}
+
+int exmc_hip_ppc_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws, int n_draws, int d,
+                      int n_chains, double* datum, double* t_obs, double* p_value, double* tstat) {
+  int rc = ppc_check(m, o, draws, n_draws, d, n_chains, datum && t_obs && p_value);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)tstat;
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t S = (size_t)n_draws, C = (size_t)n_chains, D = (size_t)d, N = (size_t)ic_n_data(m);
+  const size_t B = (C + kPpBlock - 1) / kPpBlock;
+  std::vector<double> h(S * D * C);
+  for (size_t c = 0; c < C; c++)
+    for (size_t s = 0; s < S; s++)
+      for (size_t j = 0; j < D; j++) h[(s * D + j) * C + c] = draws[(c * S + s) * D + j];
+  // scratch of the call: draws [S][d][C], sums [B][N][2], counts [B][N][2] (int64), tstat [S][4][C] where
+  // it is asked for, chain counts [4][C] (int32, last: the others stay 8-byte aligned)
+  const size_t n_ts = tstat ? S * kPpcStats * C : 0;
+  CallBuf buf;
+  rc = buf.alloc((S * D * C + 4 * B * N + n_ts) * 8 + kPpcStats * C * 4);
+  if (rc) return rc;
+  double* d_draws = buf.as<double>();
+  double* d_sums = d_draws + S * D * C;
+  int64_t* d_counts = (int64_t*)(d_sums + 2 * B * N);
+  double* d_ts = (double*)(d_counts + 2 * B * N);
+  int32_t* d_cc = (int32_t*)(d_ts + n_ts);
+  HIP_TRY(hipMemcpy(d_draws, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  std::vector<double> y(N);
+  double m0 = 0.0;
+  rc = exmc_hip_ppc(m, o, d_draws, n_draws, d, n_chains, d_sums, d_counts, d_cc, tstat ? d_ts : nullptr, t_obs, &m0,
+                    y.data());
+  if (rc) return rc;
+  std::vector<double> sums(2 * B * N);
+  std::vector<int64_t> counts(2 * B * N);
+  std::vector<int32_t> cc(kPpcStats * C);
+  HIP_TRY(hipMemcpy(sums.data(), d_sums, sums.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(counts.data(), d_counts, counts.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cc.data(), d_cc, cc.size() * 4, hipMemcpyDeviceToHost));
+  // the blocks left to right, then the finished numbers (include/exmc_hip_ppc.h)
+  const double n = (double)(S * C);
+  for (size_t i = 0; i < N; i++) {
+    double E = 0.0, E2 = 0.0;
+    int64_t n_lt = 0, n_eq = 0;
+    for (size_t b = 0; b < B; b++) {
+      E = E + sums[(b * N + i) * 2];
+      E2 = E2 + sums[(b * N + i) * 2 + 1];
+      n_lt += counts[(b * N + i) * 2];
+      n_eq += counts[(b * N + i) * 2 + 1];
+    }
+    datum[i * 4] = y[i] + E / n;
+    datum[i * 4 + 1] = (E2 - (E * E) / n) / (n - 1.0);
+    datum[i * 4 + 2] = (double)n_lt / n;
+    datum[i * 4 + 3] = (double)n_eq / n;
+  }
+  for (size_t k = 0; k < (size_t)kPpcStats; k++) {
+    int64_t above = 0;
+    for (size_t c = 0; c < C; c++) above += cc[k * C + c];
+    p_value[k] = (double)above / n;
+  }
+  if (tstat) {
+    h.resize(n_ts);
+    HIP_TRY(hipMemcpy(h.data(), d_ts, n_ts * 8, hipMemcpyDeviceToHost));
+    transpose_trace_vec(h.data(), tstat, n_draws, kPpcStats, n_chains);
+  }
 #endif
   return rc;
 }

@@ -94,13 +94,15 @@ struct StudentTParams { double df, loc, scale; };
 // consts(q, c): sample t's constants from its parameter row q (one thread per sample);
 // prepare(...): in-place rewrites of the tile (cooperative; may be empty);
 // Datum: what a lane keeps of its datum; load(i) fills it; params(dat, q, c) = the parameters of the
-// datum's distribution at the sample; term(dat, q, c) = ll_i at the sample.
+// datum's distribution at the sample; term(dat, q, c) = ll_i at the sample; obs(i) = the observed value
+// of datum i alone (the Datum's y or r: what exmc_ppc.hpp holds the replicates against).
 struct IcSimpleSrc {
   static constexpr bool kStaged = true;
   const double* y;   // dev [N]
   double log2pi32, tiny32;
   struct Datum { double y; };
   __device__ Datum load(int i) const { return {y[i]}; }
+  __device__ double obs(int i) const { return y[i]; }
   __device__ void consts(const double* q, double* c) const {
     const double sigma = exmc_exp(ic_clamp200(q[1]));
     const double ss = fmax(sigma, tiny32);
@@ -126,6 +128,7 @@ struct IcEightSchoolsSrc {
     const double sg = ys[8 + i];
     return {ys[i], sg, log2pi32 + 2.0 * exmc_log(sg), i};
   }
+  __device__ double obs(int i) const { return ys[i]; }
   __device__ void consts(const double* q, double* c) const {
     c[0] = q[0];
     c[1] = exmc_exp(ic_clamp200(q[1]));
@@ -150,6 +153,7 @@ struct IcSvSrc {
   bool ncp;          // EXMC_MODEL_SV_NCP: dims 1..99 are z_t, s_t = s_{t-1} + sigma z_t
   struct Datum { double r; int t; };
   __device__ Datum load(int i) const { return {r[i], i}; }
+  __device__ double obs(int i) const { return r[i]; }
   __device__ double lgam(double x) const {
     const double t = x + 6.5;
     double ag = lz[0];
@@ -217,6 +221,7 @@ struct IcLogisticSrc {
     a.y = y[i];
     return a;
   }
+  __device__ double obs(int i) const { return y[i]; }
   __device__ void consts(const double*, double*) const {}
   __device__ void prepare(double*, const double*, int, int, int, int) const {}
   __device__ BernoulliParams params(const Datum& a, const double* q, const double*) const {
@@ -249,6 +254,7 @@ struct IcRadonSrc {
     while (j + 1 < J && (double)i >= cs[j + 1]) j++;
     return {fl[i], y[i], j};
   }
+  __device__ double obs(int i) const { return y[i]; }
   __device__ void consts(const double* q, double* c) const {
     const double sy = exmc_exp(ic_clamp200(q[J + 3]));
     const double ssy = fmax(sy, tiny32);

@@ -4,6 +4,8 @@ device kernel.
     posterior_predictive(compiled, draws, seed=0)  -> (yrep [S][N][C] device tensor, datum names)
     posterior_predictive_blocks(compiled, draws, block_draws, seed=0) -> yields (s0, yrep block)
     as_trace(yrep, names)                          -> {name: [C][S] numpy}, the reference's map
+    ppc(compiled, draws, seed=0)                   -> posterior predictive checks of the same replicates,
+                                                      reduced on the device without the matrix
 
 The unit is the datum of a built-in kind, as in exmc_amd/model_comparison.py (include/exmc_hip_compare.h):
 one y_i, one return r_t, in the handle's datum order (`names` says which is which). `draws` is the device
@@ -84,3 +86,54 @@ def as_trace(yrep, names):
     if a.ndim != 3 or a.shape[1] != len(names):
         raise ValueError("yrep must be [S][N][C] with one name per datum")
     return {name: np.ascontiguousarray(a[:, i, :].T) for i, name in enumerate(names)}
+
+
+PPC_STATS = ("mean", "var", "min", "max")
+
+
+def ppc(compiled, draws, seed=0, chain_lo=0, tstat=False):
+    """Posterior predictive checks (include/exmc_hip_ppc.h, DESIGN.md "Posterior predictive checks"): the
+    replicates of posterior_predictive at the same seed and chain_lo, reduced in the kernel that draws
+    them; the matrix is never formed. A dict: `names` (the datums in the handle's order, as
+    posterior_predictive returns them); per datum [N] numpy `mean` and `var` of its replicates, `p_lt` and
+    `p_eq` (the share of replicates below and equal to the observation) and `pit` = p_lt + 0.5 p_eq; per
+    test statistic of a whole data set (PPC_STATS) `t_obs` (the observed value) and `p_value` (the share
+    of replicated data sets at or above it); with tstat=True also `tstat`, the device tensor [S][4][C] of
+    every replicated data set's statistics."""
+    import torch
+    N = n_data(compiled)
+    x = _device_trace(compiled, draws)
+    S, d, Cn = x.shape
+    B = (Cn + _lib.PPC_BLOCK - 1) // _lib.PPC_BLOCK
+    sums = torch.empty((B, N, 2), dtype=torch.float64, device=x.device)
+    counts = torch.empty((B, N, 2), dtype=torch.int64, device=x.device)
+    chain_counts = torch.empty((4, Cn), dtype=torch.int32, device=x.device)
+    ts = torch.empty((S, 4, Cn), dtype=torch.float64, device=x.device) if tstat else None
+    t_obs, m0, y = np.zeros(4), np.zeros(1), np.zeros(N)
+    dp = C.POINTER(C.c_double)
+    opts = _lib.PredictiveOpts(int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_lo), 0)
+    _ordered_after_torch(x)
+    compiled.check(compiled.L.exmc_hip_ppc(
+        compiled.h, opts, x.data_ptr(), S, d, Cn, sums.data_ptr(), counts.data_ptr(), chain_counts.data_ptr(),
+        None if ts is None else ts.data_ptr(), t_obs.ctypes.data_as(dp), m0.ctypes.data_as(dp), y.ctypes.data_as(dp)))
+    torch.cuda.synchronize(x.device)
+    sums, counts, chain_counts = sums.cpu().numpy(), counts.cpu().numpy(), chain_counts.cpu().numpy()
+    # the finishing expressions of include/exmc_hip_ppc.h, as exmc_hip_ppc_host writes them
+    n = np.float64(S * Cn)
+    E, E2 = np.zeros(N), np.zeros(N)
+    n_lt, n_eq = np.zeros(N, np.int64), np.zeros(N, np.int64)
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            E = E + sums[b, :, 0]
+            E2 = E2 + sums[b, :, 1]
+            n_lt = n_lt + counts[b, :, 0]
+            n_eq = n_eq + counts[b, :, 1]
+        p_lt, p_eq = n_lt.astype(np.float64) / n, n_eq.astype(np.float64) / n
+        out = dict(names=_names(compiled, N), mean=y + E / n, var=(E2 - (E * E) / n) / (n - np.float64(1.0)),
+                   p_lt=p_lt, p_eq=p_eq, pit=p_lt + 0.5 * p_eq)
+        above = chain_counts.astype(np.int64).sum(axis=1)
+        out["t_obs"] = {k: float(t_obs[i]) for i, k in enumerate(PPC_STATS)}
+        out["p_value"] = {k: float(np.float64(above[i]) / n) for i, k in enumerate(PPC_STATS)}
+    if tstat:
+        out["tstat"] = ts
+    return out
