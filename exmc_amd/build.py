@@ -22,6 +22,7 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_device.hpp"),
     os.path.join(HERE, "csrc", "exmc_ess.hpp"),
     os.path.join(HERE, "csrc", "exmc_diag.hpp"),
+    os.path.join(HERE, "csrc", "exmc_convergence.hpp"),
     os.path.join(HERE, "csrc", "exmc_host.hpp"),
     os.path.join(HERE, "csrc", "exmc_ic.hpp"),
     os.path.join(HERE, "csrc", "exmc_psis.hpp"),
@@ -42,6 +43,7 @@ DEPS = [
     os.path.join(ROOT, "include", "exmc_hip_advi.h"),
     os.path.join(ROOT, "include", "exmc_hip_predictive.h"),
     os.path.join(ROOT, "include", "exmc_hip_ppc.h"),
+    os.path.join(ROOT, "include", "exmc_hip_convergence.h"),
     os.path.join(ROOT, "include", "exmc_detmath.h"),
     os.path.join(ROOT, "include", "exmc_logtab.h"),
     os.path.join(ROOT, "include", "exmc_zig_tables.h"),

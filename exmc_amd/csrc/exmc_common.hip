@@ -1,7 +1,8 @@
 // exmc_common.hip — the model-free unit of every library: the entry points of include/exmc_hip.h
 // that name no model type, with their kernels. The native-tree seam (exmc_native_tree.hpp), the
 // fused-chain hook and the diagnostics launches behind exmc_hip_ess / _ess_bulk / _rhat
-// (exmc_diag.hpp), exmc_hip_last_error, exmc_hip_device_count. Built once to exmc_common.o and linked
+// (exmc_diag.hpp) and exmc_hip_convergence (exmc_convergence.hpp), exmc_hip_last_error,
+// exmc_hip_device_count. Built once to exmc_common.o and linked
 // into libexmc_hip.so (exmc_amd/build.py) and every plug-in (codegen.py build_plugin) next to that
 // library's exmc_hip.hip. It never sees the model handle, whose layout differs between plug-ins.
 #include "exmc_host.hpp"
@@ -12,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "exmc_convergence.hpp"
 #include "exmc_diag.hpp"
 #include "exmc_native_tree.hpp"
 
@@ -104,6 +106,125 @@ int launch_rhat(hipStream_t stream, const double* draws, int n_draws, int d, int
                      stats, rhat_dev, 1);
   HIP_TRY(hipGetLastError());
   return EXMC_OK;
+}
+
+}  // namespace host
+}  // namespace exmc
+
+// exmc_hip_convergence (include/exmc_hip_convergence.h): the dimensions in blocks whose working set
+// fits `scratch_bytes`, every block through the kernels of exmc_convergence.hpp in order. The scratch
+// lives for the call: the stream has drained before it is freed.
+namespace {
+
+struct ConvCarver {
+  char* base;
+  size_t used = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + used) : nullptr;
+    used += (count * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+};
+
+// the arrays of a block of nb dimensions, carved from `base` (null: only the size is wanted)
+size_t conv_carve(ConvBlk& g, char* base) {
+  ConvCarver c{base};
+  const size_t nb = (size_t)g.nb;
+  g.keys = c.take<double>(nb * g.P);
+  g.idx = c.take<unsigned>(nb * g.P);
+  g.z = c.take<double>(nb * g.N);
+  g.zf = c.take<double>(nb * g.N);
+  g.tile_first = c.take<int>(nb * g.n_tiles);
+  g.tile_last = c.take<int>(nb * g.n_tiles);
+  g.carry_start = c.take<int>(nb * g.n_tiles);
+  g.carry_end = c.take<int>(nb * g.n_tiles);
+  g.qs = c.take<double>(nb * 3);
+  g.nanpart = c.take<int>(nb * kConvNanSlices);
+  g.mom = c.take<double>(nb * kConvSeries * 2 * g.M);
+  g.acov = c.take<double>(nb * kConvEss * g.M * kConvLags);
+  g.state = c.take<ConvState>(nb * kConvEss);
+  return c.used;
+}
+
+// the pooled order of every dimension of the block, then the scores of its ranks into `scores`
+int conv_rank(hipStream_t stream, const ConvBlk& g, int fold, double* scores) {
+  const unsigned nb = (unsigned)g.nb;
+  hipLaunchKernelGGL(pooled_ess_fill_kernel, dim3((g.P + kConvBlock - 1) / kConvBlock, nb), dim3(kConvBlock), 0, stream, g,
+                     fold);
+  const unsigned T = g.P < (unsigned)kConvTile ? g.P : (unsigned)kConvTile;
+  const size_t lds = (size_t)T * 12;
+  hipLaunchKernelGGL(pooled_ess_sort_local_kernel, dim3(g.P / T, nb), dim3(kConvBlock), lds, stream, g, T, 2ull,
+                     (unsigned long long)T);
+  for (unsigned long long k = 2ull * T; k <= g.P; k <<= 1) {   // only above one tile: the device-wide sort
+    for (unsigned j = (unsigned)(k >> 1); j >= T; j >>= 1)
+      hipLaunchKernelGGL(pooled_ess_sort_global_kernel, dim3((g.P / 2 + kConvBlock - 1) / kConvBlock, nb), dim3(kConvBlock),
+                         0, stream, g, k, j);
+    hipLaunchKernelGGL(pooled_ess_sort_local_kernel, dim3(g.P / T, nb), dim3(kConvBlock), lds, stream, g, T, k, k);
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(pooled_ess_runs_kernel, dim3((unsigned)g.n_tiles, nb), dim3(kConvBlock), 0, stream, g, 0,
+                     (double*)nullptr);
+  hipLaunchKernelGGL(pooled_ess_carry_kernel, dim3((nb + 63) / 64), dim3(64), 0, stream, g);
+  hipLaunchKernelGGL(pooled_ess_runs_kernel, dim3((unsigned)g.n_tiles, nb), dim3(kConvBlock), 0, stream, g, 1, scores);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+
+}  // namespace
+
+namespace exmc {
+namespace host __attribute__((visibility("hidden"))) {
+
+int launch_convergence(hipStream_t stream, hipEvent_t start, const double* draws, int n_draws, int d,
+                       int n_chains, size_t scratch_bytes, double* out_dev) {
+  ConvBlk g{};
+  g.draws = draws;
+  g.D = d;
+  g.C = n_chains;
+  g.n = n_draws / 2;
+  g.M = 2 * n_chains;
+  g.N = g.M * g.n;   // the caller has checked that it fits
+  g.P = 2;
+  while (g.P < (unsigned)g.N) g.P <<= 1;
+  g.n_tiles = (int)(((long long)g.N + kConvRunTile - 1) / kConvRunTile);
+  g.nb = 1;
+  const size_t per_dim = conv_carve(g, nullptr);
+  size_t nb = scratch_bytes / per_dim;
+  nb = nb < 1 ? 1 : (nb > (size_t)d ? (size_t)d : nb);
+  if (nb > 32768) nb = 32768;   // a block's dimensions are a grid's y
+  g.nb = (int)nb;
+  CallBuf buf;
+  int rc = buf.alloc(conv_carve(g, nullptr));
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(start, stream));   // the caller's timing covers the launches, not the allocation
+  const int nb_full = g.nb;
+  for (int dim0 = 0; dim0 < d && !rc; dim0 += nb_full) {
+    g.dim0 = dim0;
+    g.nb = (d - dim0 < nb_full) ? (d - dim0) : nb_full;
+    conv_carve(g, (char*)buf.p);   // a shorter last block is carved more tightly, inside the same buffer
+    const unsigned ub = (unsigned)g.nb;
+    HIP_TRY(hipMemsetAsync(g.state, 0, (size_t)g.nb * kConvEss * sizeof(ConvState), stream));
+    hipLaunchKernelGGL(pooled_ess_nan_kernel, dim3(kConvNanSlices, ub), dim3(kConvBlock), 0, stream, g);
+    rc = conv_rank(stream, g, 0, g.z);
+    if (rc) break;
+    hipLaunchKernelGGL(pooled_ess_quantile_kernel, dim3((ub + 63) / 64), dim3(64), 0, stream, g);
+    rc = conv_rank(stream, g, 1, g.zf);
+    if (rc) break;
+    hipLaunchKernelGGL(pooled_ess_moments_kernel, dim3((unsigned)((g.M + kConvBlock - 1) / kConvBlock), ub, kConvSeries),
+                       dim3(kConvBlock), 0, stream, g);
+    // every block of lags is launched; a (dimension, series) that has met its cut leaves at once. The
+    // last block holds the pair at which `2 j + 1 <= n - 1` fails, so every series ends.
+    for (int l0 = 0; l0 <= g.n; l0 += kConvLags) {
+      hipLaunchKernelGGL(pooled_ess_acov_kernel, dim3((unsigned)((g.M + 63) / 64), ub, kConvEss), dim3(64), 0, stream, g, l0);
+      hipLaunchKernelGGL(pooled_ess_decide_kernel, dim3(ub * kConvEss), dim3(64), 0, stream, g, l0);
+    }
+    hipLaunchKernelGGL(pooled_ess_finish_kernel, dim3((ub + 63) / 64), dim3(64), 0, stream, g, out_dev);
+    if (hipGetLastError() != hipSuccess) rc = fail(EXMC_ERR_HIP, "convergence: a launch failed");
+  }
+  const hipError_t e = hipStreamSynchronize(stream);   // before the scratch goes
+  if (!rc && e != hipSuccess) rc = fail(EXMC_ERR_HIP, std::string("convergence: ") + hipGetErrorString(e));
+  return rc;
 }
 
 }  // namespace host

@@ -13,6 +13,7 @@
 #include "../../include/exmc_hip_advi.h"
 #include "../../include/exmc_hip_predictive.h"
 #include "../../include/exmc_hip_ppc.h"
+#include "../../include/exmc_hip_convergence.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1936,6 +1937,47 @@ int exmc_hip_rhat(exmc_hip_model* m, const double* draws_dev, int n_draws, int d
   if (rc) return rc;
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
   return finish_timing(m);
+}
+
+// include/exmc_hip_convergence.h: the kernels and their scratch are exmc_common.hip's; nothing of the
+// handle but its device, stream and events is touched
+int exmc_hip_convergence(exmc_hip_model* m, const double* draws_dev, int n_draws, int d, int n_chains,
+                         size_t scratch_bytes, double* out_dev) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  if (!draws_dev || !out_dev || n_draws < 8 || d < 1 || n_chains < 1)
+    return fail(EXMC_ERR_BADARG, "convergence: need a trace, an output, n_draws >= 8, d >= 1 and n_chains >= 1");
+  if (2LL * n_chains * (n_draws / 2) > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "convergence: more than 2^31 - 1 pooled draws per dimension");
+  HIP_TRY(hipSetDevice(m->device));
+  int rc = launch_convergence(m->stream, m->ev0, draws_dev, n_draws, d, n_chains,
+                              scratch_bytes ? scratch_bytes : (size_t)EXMC_CONVERGENCE_DEFAULT_SCRATCH, out_dev);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);
+}
+
+int exmc_hip_convergence_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d, int n_chains,
+                              size_t scratch_bytes, double* out_host) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  if (!draws_host || !out_host || n_draws < 8 || d < 1 || n_chains < 1)
+    return fail(EXMC_ERR_BADARG, "convergence: need a trace, an output, n_draws >= 8, d >= 1 and n_chains >= 1");
+  if (2LL * n_chains * (n_draws / 2) > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "convergence: more than 2^31 - 1 pooled draws per dimension");
+  HIP_TRY(hipSetDevice(m->device));
+  const int S = n_draws, C = n_chains;
+  std::vector<double> h((size_t)S * d * C);   // [C][S][d] -> [S][d][C]
+  for (int c = 0; c < C; c++)
+    for (int s = 0; s < S; s++)
+      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
+  CallBuf buf;
+  int rc = buf.alloc((h.size() + (size_t)EXMC_CONVERGENCE_NOUT * d) * 8);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  double* out = buf.as<double>() + h.size();
+  rc = exmc_hip_convergence(m, buf.as<double>(), S, d, C, scratch_bytes, out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(out_host, out, (size_t)EXMC_CONVERGENCE_NOUT * d * 8, hipMemcpyDeviceToHost));
+  return EXMC_OK;
 }
 
 }  // extern "C"

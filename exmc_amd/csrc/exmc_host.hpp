@@ -74,6 +74,11 @@ int launch_rank_scores(hipStream_t stream, const double* draws, int n_draws, int
 // Diagnostics.rhat of every dimension; `stats`: scratch of d * 4 * n_chains doubles
 int launch_rhat(hipStream_t stream, const double* draws, int n_draws, int d, int n_chains, double* stats,
                 double* rhat_dev);
+// exmc_hip_convergence over draws [S][D][C] into out_dev [6][D]; allocates its scratch (at most
+// `scratch_bytes`, never less than one dimension's), records `start` in front of the first launch and
+// returns when the stream has drained
+int launch_convergence(hipStream_t stream, hipEvent_t start, const double* draws, int n_draws, int d,
+                       int n_chains, size_t scratch_bytes, double* out_dev);
 
 }  // namespace host
 }  // namespace exmc

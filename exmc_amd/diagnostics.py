@@ -5,6 +5,9 @@
     rhat(compiled, draws)      -> [d]      split R-hat over the chains           diagnostics.ex:80-115
     summary(compiled, draws, names) -> {name: {mean, std, q5, q25, q50, q75, q95} + ess, ess_bulk,
                                         rhat}                                     diagnostics.ex:14-34
+    convergence(compiled, draws) -> {rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean,
+                                     rhat: [d]}   ACROSS chains: ranks over the pooled draws of all chains
+                                     (include/exmc_hip_convergence.h; not in the reference)
 
 `draws` is the device trace the sampling kernels write, a float64 CUDA tensor [S][d][C], or a host
 array [C][S][d] (the layout of the `_host` entry points and of `stats["raw"]["draws"]`), which is
@@ -91,3 +94,30 @@ def summary(compiled, draws, names=None):
                            q25=float(qs[1, i]), q50=float(qs[2, i]), q75=float(qs[3, i]),
                            q95=float(qs[4, i]), ess=float(e[i]), ess_bulk=float(eb[i]),
                            rhat=float(r[i])) for i in range(d)}
+
+
+def convergence(compiled, draws, names=None, scratch_bytes=0):
+    """The convergence diagnostics across chains of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021)
+    (include/exmc_hip_convergence.h, DESIGN.md "Convergence diagnostics across chains"): per dimension the
+    rank-normalised and the folded split R-hat, bulk, tail and mean ESS and the Monte Carlo standard error
+    of the mean, all over the pooled draws of every chain, plus rhat = max(rhat_bulk, rhat_tail) (NaN if
+    either is). A dict of [d] arrays; with `names`, {name: {row: float}}. `scratch_bytes` bounds the
+    device scratch of the call (0: the library's default); the result does not depend on it."""
+    import torch
+    from . import _lib
+    x = _device_trace(compiled, draws)
+    S, d, C = x.shape
+    out = torch.empty((len(_lib.CONVERGENCE_ROWS), d), dtype=torch.float64, device=x.device)
+    _ordered_after_torch(x)
+    compiled.check(compiled.L.exmc_hip_convergence(compiled.h, x.data_ptr(), S, d, C, int(scratch_bytes),
+                                                   out.data_ptr()))
+    torch.cuda.synchronize(x.device)
+    rows = dict(zip(_lib.CONVERGENCE_ROWS, out.cpu().numpy()))
+    either = np.isnan(rows["rhat_bulk"]) | np.isnan(rows["rhat_tail"])
+    rows["rhat"] = np.where(either, np.nan, np.fmax(rows["rhat_bulk"], rows["rhat_tail"]))
+    if names is None:
+        return rows
+    names = list(names)
+    if len(names) != d:
+        raise ValueError("%d names for %d dimensions" % (len(names), d))
+    return {names[i]: {k: float(v[i]) for k, v in rows.items()} for i in range(d)}
