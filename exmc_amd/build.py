@@ -24,6 +24,7 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_diag.hpp"),
     os.path.join(HERE, "csrc", "exmc_convergence.hpp"),
     os.path.join(HERE, "csrc", "exmc_host.hpp"),
+    os.path.join(HERE, "csrc", "exmc_layout_host.hpp"),
     os.path.join(HERE, "csrc", "exmc_ic.hpp"),
     os.path.join(HERE, "csrc", "exmc_psis.hpp"),
     os.path.join(HERE, "csrc", "exmc_gen_pointwise.hpp"),

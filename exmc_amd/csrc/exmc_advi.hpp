@@ -58,10 +58,7 @@ struct AdviParams {
   double* log_sigma;      // [D][C] or null
   int32_t* num_iters;     // [C] or null
   int32_t* converged;     // [C] or null
-  const uint64_t* zig_ki;
-  const double* zig_wi;
-  const double* zig_fi;
-  double nor_r;
+  RngArgs rng;
   FlatOrder flat;
 };
 
@@ -78,7 +75,7 @@ __global__ void __launch_bounds__(64) advi_kernel(AdviParams P, typename M::Cons
   typename M::Lane ln;
   M::load(mc, l, ln);
   attach_scratch<M>(ln, xlds);
-  const ZigTables zt{P.zig_ki, P.zig_wi, P.zig_fi};
+  const ZigTables zt{P.rng.ki, P.rng.wi, P.rng.fi};
   const uint64_t seed = P.base_seed + 7919ULL * (uint64_t)(P.chain_lo + chain);
 
   bool valid[DPL];
@@ -123,7 +120,7 @@ __global__ void __launch_bounds__(64) advi_kernel(AdviParams P, typename M::Cons
       for (int k = 0; k < DPL; k++) eps[k] = g[k] = 0.0;
       if (active) {   // the generator of a converged fit stays where its halt left it
         for (int r = 0; r < D; r++) {
-          const double v = rng_normal(rng, zt, P.nor_r);
+          const double v = rng_normal(rng, zt, P.rng.nor_r);
 #pragma unroll
           for (int k = 0; k < DPL; k++)
             if (rank[k] == r) eps[k] = v;
@@ -195,7 +192,7 @@ __global__ void __launch_bounds__(64) advi_kernel(AdviParams P, typename M::Cons
 #pragma unroll
     for (int k = 0; k < DPL; k++) dr[k] = 0.0;
     for (int r = 0; r < D; r++) {
-      const double v = rng_normal(rng, zt, P.nor_r);
+      const double v = rng_normal(rng, zt, P.rng.nor_r);
 #pragma unroll
       for (int k = 0; k < DPL; k++)
         if (rank[k] == r) dr[k] = mu[k] + sigma[k] * v;

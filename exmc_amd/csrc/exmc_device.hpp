@@ -613,6 +613,14 @@ struct ZigTables {
   const double* fi;
 };
 
+// the handle's tables and the tail bound as one kernel argument (the host's rng_args fills it)
+struct RngArgs {
+  const uint64_t* ki;
+  const double* wi;
+  const double* fi;
+  double nor_r;
+};
+
 // :rand.normal_s — 256-layer ziggurat on one 58-bit word (bit 6 sign, bits 7..57 the
 // 51-bit R whose low 8 bits select the layer).
 // (words: incremented by the number of generator words the draw consumed -- one when the first word is

@@ -32,6 +32,7 @@
 #include "../../include/exmc_zig_tables.h"
 #include "exmc_kernels.hpp"
 #include "exmc_host.hpp"
+#include "exmc_layout_host.hpp"
 #include "exmc_ic.hpp"
 #include "exmc_psis.hpp"
 
@@ -383,6 +384,7 @@ int set_flat_order(exmc_hip_model* m, const int32_t* perm) {
 const uint64_t* zig_ki(exmc_hip_model* m) { return m->zig.as<uint64_t>(); }
 const double* zig_wi(exmc_hip_model* m) { return m->zig.as<double>() + 256; }
 const double* zig_fi(exmc_hip_model* m) { return m->zig.as<double>() + 512; }
+RngArgs rng_args(exmc_hip_model* m) { return RngArgs{zig_ki(m), zig_wi(m), zig_fi(m), EXMC_NOR_R}; }
 
 // one_chain: the start of the shared warmup (a generated lane layout may have its one-chain form)
 int launch_init(exmc_hip_model* m, int lanes, int C, int chain_lo, uint64_t seed,
@@ -590,17 +592,44 @@ int finish_timing(exmc_hip_model* m) {
   return EXMC_OK;
 }
 
-// [C][n][d] host <- [n][d][C] device-layout host copy
-void transpose_trace_vec(const double* src, double* dst, int n, int d, int C) {
-  for (int s = 0; s < n; s++)
-    for (int i = 0; i < d; i++)
-      for (int c = 0; c < C; c++) dst[((size_t)c * n + s) * d + i] = src[((size_t)s * d + i) * C + c];
-}
-template <class T>
-void transpose_trace_scalar(const T* src, T* dst, int n, int C) {
-  for (int s = 0; s < n; s++)
-    for (int c = 0; c < C; c++) dst[(size_t)c * n + s] = src[(size_t)s * C + c];
-}
+// The scratch of a _host form: consecutive typed slices of one device buffer and of their host mirror,
+// behind the caller's trace where the form takes one. take() describes the slices (8-byte types first),
+// alloc() or alloc_with_trace() makes the buffer, dev() points into it, download() fills the mirror of the
+// slices and host() points into that. (The layout loops are exmc_layout_host.hpp.)
+struct Scratch {
+  template <class T>
+  struct Slice { size_t off; };
+  CallBuf buf;
+  std::vector<char> mirror;
+  size_t front = 0, bytes = 0;   // of the trace, of the slices
+  template <class T>
+  Slice<T> take(size_t n) {
+    const Slice<T> s{bytes};
+    bytes += n * sizeof(T);
+    return s;
+  }
+  int alloc() { return buf.alloc(front + bytes); }
+  // ... with the caller's trace [C][S][d] in the device layout [S][d][C] in front: trace()
+  int alloc_with_trace(const double* draws_host, int S, int d, int C) {
+    std::vector<double> h((size_t)S * d * C);
+    chains_last(draws_host, h.data(), S, d, C);
+    front = h.size() * 8;
+    int rc = alloc();
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(buf.p, h.data(), front, hipMemcpyHostToDevice));
+    return EXMC_OK;
+  }
+  const double* trace() const { return buf.as<double>(); }
+  int download() {
+    mirror.resize(bytes);
+    HIP_TRY(hipMemcpy(mirror.data(), buf.as<char>() + front, bytes, hipMemcpyDeviceToHost));
+    return EXMC_OK;
+  }
+  template <class T>
+  T* dev(Slice<T> s) const { return (T*)(buf.as<char>() + front + s.off); }
+  template <class T>
+  const T* host(Slice<T> s) const { return (const T*)(mirror.data() + s.off); }
+};
 
 struct TraceLayout {
   size_t off_draws, off_logp, off_depth, off_nsteps, off_div, off_acc, off_energy, total;
@@ -1964,19 +1993,14 @@ int exmc_hip_convergence_host(exmc_hip_model* m, const double* draws_host, int n
   if (2LL * n_chains * (n_draws / 2) > 0x7FFFFFFFLL)
     return fail(EXMC_ERR_BADARG, "convergence: more than 2^31 - 1 pooled draws per dimension");
   HIP_TRY(hipSetDevice(m->device));
-  const int S = n_draws, C = n_chains;
-  std::vector<double> h((size_t)S * d * C);   // [C][S][d] -> [S][d][C]
-  for (int c = 0; c < C; c++)
-    for (int s = 0; s < S; s++)
-      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
-  CallBuf buf;
-  int rc = buf.alloc((h.size() + (size_t)EXMC_CONVERGENCE_NOUT * d) * 8);
+  const size_t n_out = (size_t)EXMC_CONVERGENCE_NOUT * d;
+  Scratch sc;
+  const auto s_out = sc.take<double>(n_out);
+  int rc = sc.alloc_with_trace(draws_host, n_draws, d, n_chains);
+  if (!rc) rc = exmc_hip_convergence(m, sc.trace(), n_draws, d, n_chains, scratch_bytes, sc.dev(s_out));
+  if (!rc) rc = sc.download();
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-  double* out = buf.as<double>() + h.size();
-  rc = exmc_hip_convergence(m, buf.as<double>(), S, d, C, scratch_bytes, out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(out_host, out, (size_t)EXMC_CONVERGENCE_NOUT * d * 8, hipMemcpyDeviceToHost));
+  std::copy(sc.host(s_out), sc.host(s_out) + n_out, out_host);
   return EXMC_OK;
 }
 
@@ -2207,18 +2231,22 @@ int ic_with_src(exmc_hip_model* m, F&& f) {
   }
 }
 
-// posterior predictive replicates of the kind's datums (predictive_kernel, exmc_predictive.hpp): one
-// wavefront per 64 chains, between the handle's events
-template <class Src>
-int predictive_launch(exmc_hip_model* m, const Src& src, const PredictiveParams& P) {
-  const size_t lds = pp_lds_bytes(m->d);
-  if (lds > 64 * 1024) EXMC_KMAXLDS(predictive_kernel<Src>, lds);
-  const unsigned blocks = (unsigned)((P.C + kPpBlock - 1) / kPpBlock);
+// predictive_kernel<Src> or ppc_kernel<Src> (exmc_predictive.hpp, exmc_ppc.hpp) with `lds` bytes of
+// dynamic LDS: one wavefront per 64 chains, between the handle's events
+template <class Src, class Params>
+int pp_launch(exmc_hip_model* m, void (*kernel)(Src, Params), size_t lds, const Src& src, const Params& P) {
+  if (lds > 64 * 1024) EXMC_KMAXLDS(kernel, lds);
   HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  hipLaunchKernelGGL(predictive_kernel<Src>, dim3(blocks), dim3(kPpBlock), lds, m->stream, src, P);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((P.C + kPpBlock - 1) / kPpBlock)), dim3(kPpBlock), lds, m->stream, src, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
   return finish_timing(m);   // waits for the kernel: before the source's data image is freed
+}
+
+// posterior predictive replicates of the kind's datums
+template <class Src>
+int predictive_launch(exmc_hip_model* m, const Src& src, const PredictiveParams& P) {
+  return pp_launch(m, predictive_kernel<Src>, pp_lds_bytes(m->d), src, P);
 }
 
 // the observed values of the kind's datums in the handle's order (ppc_obs_kernel), on the host
@@ -2253,8 +2281,7 @@ void ppc_tstat(const double* v, int N, double m0, double* T) {
   T[3] = mx;
 }
 
-// posterior predictive checks (ppc_kernel, exmc_ppc.hpp): the observed values and their statistics first,
-// then one wavefront per 64 chains between the handle's events
+// posterior predictive checks: the observed values and their statistics first, then the launch
 template <class Src>
 int ppc_launch(exmc_hip_model* m, const Src& src, PpcParams& P, double* y) {
   int rc = ppc_observed(m, src, P.N, y);
@@ -2263,14 +2290,7 @@ int ppc_launch(exmc_hip_model* m, const Src& src, PpcParams& P, double* y) {
   for (int i = 0; i < P.N; i++) sum = sum + y[i];
   P.m0 = sum / (double)P.N;
   ppc_tstat(y, P.N, P.m0, P.t_obs);
-  const size_t lds = ppc_lds_bytes(m->d);
-  if (lds > 64 * 1024) EXMC_KMAXLDS(ppc_kernel<Src>, lds);
-  const unsigned blocks = (unsigned)((P.C + kPpBlock - 1) / kPpBlock);
-  HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  hipLaunchKernelGGL(ppc_kernel<Src>, dim3(blocks), dim3(kPpBlock), lds, m->stream, src, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(m->ev1, m->stream));
-  return finish_timing(m);   // waits for the kernel: before the source's data image is freed
+  return pp_launch(m, ppc_kernel<Src>, ppc_lds_bytes(m->d), src, P);
 }
 
 #endif
@@ -2336,19 +2356,13 @@ int ic_from_host(exmc_hip_model* m, const double* draws_host, int n_draws, int d
   if (!draws_host || !out_host || d != m->d || n_draws < 1 || n_chains < 1 || (long long)n_draws * n_chains < 2)
     return fail(EXMC_ERR_BADARG, "model comparison: bad arguments");
   HIP_TRY(hipSetDevice(m->device));
-  const int S = n_draws, C = n_chains;
-  std::vector<double> h((size_t)S * d * C);
-  for (int c = 0; c < C; c++)
-    for (int s = 0; s < S; s++)
-      for (int j = 0; j < d; j++) h[((size_t)s * d + j) * C + c] = draws_host[((size_t)c * S + s) * d + j];
-  CallBuf buf;
-  int rc = buf.alloc((h.size() + (size_t)rows * N) * 8);
+  Scratch sc;
+  const auto s_out = sc.take<double>((size_t)rows * N);
+  int rc = sc.alloc_with_trace(draws_host, n_draws, d, n_chains);
+  if (!rc) rc = run(sc.trace(), sc.dev(s_out));
+  if (!rc) rc = sc.download();
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(buf.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-  double* out = buf.as<double>() + h.size();
-  rc = run(buf.as<double>(), out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(out_host, out, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
+  std::copy(sc.host(s_out), sc.host(s_out) + (size_t)rows * N, out_host);
   return EXMC_OK;
 }
 
@@ -2444,6 +2458,10 @@ int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, i
 #endif
 }
 
+}  // extern "C"
+
+namespace {
+
 // ---- what Pathfinder and ADVI share: one fit per lane group, one launch -----------------------------
 // KERNEL<M, G> of the handle's layout over n lane groups, one wavefront per workgroup (the launch shape of
 // init_chains_kernel), between the handle's events
@@ -2459,25 +2477,64 @@ int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, i
     return (int)EXMC_OK;                                                                               \
   })
 
-}  // extern "C"
-// a device result [rows][C] (fit the fastest index) into the host's [C][rows]; dst may be null
-template <class T>
-static void fits_first(const T* src, T* dst, size_t rows, size_t C) {
-  if (!dst) return;
-  for (size_t c = 0; c < C; c++)
-    for (size_t i = 0; i < rows; i++) dst[c * rows + i] = src[i * C + c];
+int pf_check(exmc_hip_model* m, const exmc_hip_pf_opts& o, int n_paths, int chain_lo) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  static_assert(EXMC_PF_MAX_HISTORY == kPfHistory, "the header states the kernel's bound");
+  if (o.max_iters < 1 || o.num_draws < 1 || o.history_size < 1 || o.history_size > kPfHistory)
+    return fail(EXMC_ERR_BADARG, "pathfinder: max_iters >= 1, num_draws >= 1 and 1 <= history_size <= 6");
+  if (n_paths < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "pathfinder: bad arguments");
+  return EXMC_OK;
 }
+
+int advi_check(exmc_hip_model* m, const exmc_hip_advi_opts& o, int n_fits, int chain_lo) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  if (o.max_iters < 1 || o.num_draws < 1 || o.num_mc_samples < 1 || o.window_size < 2)
+    return fail(EXMC_ERR_BADARG, "advi: max_iters >= 1, num_draws >= 1, num_mc_samples >= 1 and window_size >= 2");
+  if (n_fits < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "advi: bad arguments");
+  return EXMC_OK;
+}
+
+// what exmc_hip_posterior_predictive and exmc_hip_ppc (and their _host forms) ask of their arguments;
+// `what` opens the messages, `own_bad` is the entry point's own clause of the argument check
+int pp_check(exmc_hip_model* m, const char* what, const exmc_hip_predictive_opts& o, const void* draws, int n_draws,
+             int d, int n_chains, bool own_bad) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)o; (void)draws; (void)n_draws; (void)d; (void)n_chains; (void)own_bad;
+  return fail(EXMC_ERR_UNSUPPORTED, std::string(what) + ": generated models are not supported");
+#else
+  if (m->kind == EXMC_MODEL_CUSTOM || ic_n_data(m) < 0)
+    return fail(EXMC_ERR_UNSUPPORTED, std::string(what) + ": this model kind has no built-in datums");
+  if (!draws || d != m->d || n_draws < 1 || n_chains < 1 || o.chain_lo < 0 || own_bad)
+    return fail(EXMC_ERR_BADARG, std::string(what) + ": bad arguments");
+  return EXMC_OK;
+#endif
+}
+
+// the fields PredictiveParams and PpcParams share
+template <class Params>
+void pp_fill(Params& P, exmc_hip_model* m, const exmc_hip_predictive_opts& o, const double* draws_dev, int n_draws,
+             int d, int n_chains) {
+  P.draws = draws_dev;
+  P.S = n_draws;
+  P.d = d;
+  P.C = n_chains;
+  P.N = ic_n_data(m);
+  P.chain_lo = o.chain_lo;
+  P.base_seed = o.seed;
+  P.rng = rng_args(m);
+}
+
+}  // namespace
+
 extern "C" {
 
 // ---- Pathfinder (include/exmc_hip_pathfinder.h; pathfinder_kernel, exmc_pathfinder.hpp) --------------
 int exmc_hip_pathfinder(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int chain_lo, double* draws_dev,
                         double* mu_dev, double* sigma_dev, double* elbo_dev, int32_t* num_iters_dev,
                         int32_t* best_index_dev, int32_t* status_dev) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-  static_assert(EXMC_PF_MAX_HISTORY == kPfHistory, "the header states the kernel's bound");
-  if (o.max_iters < 1 || o.num_draws < 1 || o.history_size < 1 || o.history_size > kPfHistory)
-    return fail(EXMC_ERR_BADARG, "pathfinder: max_iters >= 1, num_draws >= 1 and 1 <= history_size <= 6");
-  if (n_paths < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "pathfinder: bad arguments");
+  int rc = pf_check(m, o, n_paths, chain_lo);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(m->device));
   const int lanes = resolve_lanes(m, o.lanes_per_chain);
   PathfinderParams P;
@@ -2495,10 +2552,9 @@ int exmc_hip_pathfinder(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int 
   P.num_iters = num_iters_dev;
   P.best_index = best_index_dev;
   P.status = status_dev;
-  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
-  P.nor_r = EXMC_NOR_R;
+  P.rng = rng_args(m);
   P.flat = flat_order(m);
-  int rc = EXMC_FIT_LAUNCH(m, lanes, pathfinder_kernel, n_paths, P);
+  rc = EXMC_FIT_LAUNCH(m, lanes, pathfinder_kernel, n_paths, P);
   if (rc) return rc;
   return finish_timing(m);   // waits for the launch
 }
@@ -2506,50 +2562,31 @@ int exmc_hip_pathfinder(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int 
 int exmc_hip_pathfinder_host(exmc_hip_model* m, exmc_hip_pf_opts o, int n_paths, int chain_lo, double* draws,
                              double* mu, double* sigma, double* elbo, int32_t* num_iters, int32_t* best_index,
                              int32_t* status) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-  if (o.max_iters < 1 || o.num_draws < 1 || o.history_size < 1 || o.history_size > kPfHistory)
-    return fail(EXMC_ERR_BADARG, "pathfinder: max_iters >= 1, num_draws >= 1 and 1 <= history_size <= 6");
-  if (n_paths < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "pathfinder: bad arguments");
+  int rc = pf_check(m, o, n_paths, chain_lo);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(m->device));
   const size_t C = (size_t)n_paths, d = (size_t)m->d, S = (size_t)o.num_draws;
-  // scratch of the call: draws [S][d][C], mu [d][C], sigma [d][C], elbo [C], three int32 [C]
-  const size_t n_dbl = (draws ? S * d * C : 0) + 2 * d * C + C;
-  CallBuf buf;
-  int rc = buf.alloc(n_dbl * 8 + 3 * C * 4);
+  Scratch sc;
+  const auto s_draws = sc.take<double>(draws ? S * d * C : 0);   // [S][d][C]
+  const auto s_mu = sc.take<double>(d * C), s_sigma = sc.take<double>(d * C), s_elbo = sc.take<double>(C);
+  const auto s_iters = sc.take<int32_t>(C), s_best = sc.take<int32_t>(C), s_status = sc.take<int32_t>(C);
+  rc = sc.alloc();
   if (rc) return rc;
-  double* d_draws = draws ? buf.as<double>() : nullptr;
-  double* d_mu = buf.as<double>() + (draws ? S * d * C : 0);
-  double* d_sigma = d_mu + d * C;
-  double* d_elbo = d_sigma + d * C;
-  int32_t* d_int = (int32_t*)(d_elbo + C);
-  rc = exmc_hip_pathfinder(m, o, n_paths, chain_lo, d_draws, d_mu, d_sigma, d_elbo, d_int, d_int + C, d_int + 2 * C);
+  rc = exmc_hip_pathfinder(m, o, n_paths, chain_lo, draws ? sc.dev(s_draws) : nullptr, sc.dev(s_mu), sc.dev(s_sigma),
+                           sc.dev(s_elbo), sc.dev(s_iters), sc.dev(s_best), sc.dev(s_status));
+  if (!rc) rc = sc.download();
   if (rc) return rc;
-  std::vector<double> h(n_dbl);
-  std::vector<int32_t> hi(3 * C);
-  HIP_TRY(hipMemcpy(h.data(), buf.p, n_dbl * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hi.data(), d_int, 3 * C * 4, hipMemcpyDeviceToHost));
-  const double* h_mu = h.data() + (draws ? S * d * C : 0);
-  const double* h_sigma = h_mu + d * C;
-  const double* h_elbo = h_sigma + d * C;
-  if (draws) transpose_trace_vec(h.data(), draws, o.num_draws, m->d, n_paths);
-  fits_first(h_mu, mu, d, C);
-  fits_first(h_sigma, sigma, d, C);
-  fits_first(h_elbo, elbo, 1, C);
-  fits_first(hi.data(), num_iters, 1, C);
-  fits_first(hi.data() + C, best_index, 1, C);
-  fits_first(hi.data() + 2 * C, status, 1, C);
+  if (draws) transpose_trace_vec(sc.host(s_draws), draws, o.num_draws, m->d, n_paths);
+  fits_first(sc.host(s_mu), mu, d, C);
+  fits_first(sc.host(s_sigma), sigma, d, C);
+  fits_first(sc.host(s_elbo), elbo, 1, C);
+  fits_first(sc.host(s_iters), num_iters, 1, C);
+  fits_first(sc.host(s_best), best_index, 1, C);
+  fits_first(sc.host(s_status), status, 1, C);
   return EXMC_OK;
 }
 
 // ---- ADVI (include/exmc_hip_advi.h; advi_kernel, exmc_advi.hpp) --------------------------------------
-static int advi_check(exmc_hip_model* m, const exmc_hip_advi_opts& o, int n_fits, int chain_lo) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-  if (o.max_iters < 1 || o.num_draws < 1 || o.num_mc_samples < 1 || o.window_size < 2)
-    return fail(EXMC_ERR_BADARG, "advi: max_iters >= 1, num_draws >= 1, num_mc_samples >= 1 and window_size >= 2");
-  if (n_fits < 1 || chain_lo < 0) return fail(EXMC_ERR_BADARG, "advi: bad arguments");
-  return EXMC_OK;
-}
-
 int exmc_hip_advi(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int chain_lo, double* draws_dev,
                   double* mu_dev, double* log_sigma_dev, double* elbo_history_dev, int32_t* num_iters_dev,
                   int32_t* converged_dev) {
@@ -2581,8 +2618,7 @@ int exmc_hip_advi(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int chain
   P.log_sigma = log_sigma_dev;
   P.num_iters = num_iters_dev;
   P.converged = converged_dev;
-  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
-  P.nor_r = EXMC_NOR_R;
+  P.rng = rng_args(m);
   P.flat = flat_order(m);
   rc = EXMC_FIT_LAUNCH(m, lanes, advi_kernel, n_fits, P);
   if (rc) return rc;
@@ -2596,68 +2632,39 @@ int exmc_hip_advi_host(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int 
   if (rc) return rc;
   HIP_TRY(hipSetDevice(m->device));
   const size_t C = (size_t)n_fits, d = (size_t)m->d, S = (size_t)o.num_draws, I = (size_t)o.max_iters;
-  // scratch of the call: draws [S][d][C], history [I][C], mu [d][C], log_sigma [d][C], two int32 [C]
-  const size_t n_draws = draws ? S * d * C : 0, n_hist = elbo_history ? I * C : 0;
-  const size_t n_dbl = n_draws + n_hist + 2 * d * C;
-  CallBuf buf;
-  rc = buf.alloc(n_dbl * 8 + 2 * C * 4);
+  Scratch sc;
+  const auto s_draws = sc.take<double>(draws ? S * d * C : 0);     // [S][d][C]
+  const auto s_hist = sc.take<double>(elbo_history ? I * C : 0);   // [I][C]
+  const auto s_mu = sc.take<double>(d * C), s_ls = sc.take<double>(d * C);
+  const auto s_iters = sc.take<int32_t>(C), s_conv = sc.take<int32_t>(C);
+  rc = sc.alloc();
   if (rc) return rc;
-  double* d_draws = buf.as<double>();
-  double* d_hist = d_draws + n_draws;
-  double* d_mu = d_hist + n_hist;
-  double* d_ls = d_mu + d * C;
-  int32_t* d_int = (int32_t*)(d_ls + d * C);
-  rc = exmc_hip_advi(m, o, n_fits, chain_lo, draws ? d_draws : nullptr, d_mu, d_ls,
-                     elbo_history ? d_hist : nullptr, d_int, d_int + C);
+  rc = exmc_hip_advi(m, o, n_fits, chain_lo, draws ? sc.dev(s_draws) : nullptr, sc.dev(s_mu), sc.dev(s_ls),
+                     elbo_history ? sc.dev(s_hist) : nullptr, sc.dev(s_iters), sc.dev(s_conv));
+  if (!rc) rc = sc.download();
   if (rc) return rc;
-  std::vector<double> h(n_dbl);
-  std::vector<int32_t> hi(2 * C);
-  HIP_TRY(hipMemcpy(h.data(), buf.p, n_dbl * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hi.data(), d_int, 2 * C * 4, hipMemcpyDeviceToHost));
-  if (draws) transpose_trace_vec(h.data(), draws, o.num_draws, m->d, n_fits);
-  fits_first(h.data() + n_draws, elbo_history, I, C);
-  fits_first(h.data() + n_draws + n_hist, mu, d, C);
-  fits_first(h.data() + n_draws + n_hist + d * C, log_sigma, d, C);
-  fits_first(hi.data(), num_iters, 1, C);
-  fits_first(hi.data() + C, converged, 1, C);
+  if (draws) transpose_trace_vec(sc.host(s_draws), draws, o.num_draws, m->d, n_fits);
+  fits_first(sc.host(s_hist), elbo_history, I, C);
+  fits_first(sc.host(s_mu), mu, d, C);
+  fits_first(sc.host(s_ls), log_sigma, d, C);
+  fits_first(sc.host(s_iters), num_iters, 1, C);
+  fits_first(sc.host(s_conv), converged, 1, C);
   return EXMC_OK;
 }
 
 // ---- posterior predictive (include/exmc_hip_predictive.h; predictive_kernel, exmc_predictive.hpp) ------
-static int predictive_check(exmc_hip_model* m, const exmc_hip_predictive_opts& o, const void* draws, int n_draws,
-                            int d, int n_chains, const void* rng_state, const void* yrep) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-#ifdef EXMC_ONLY_CUSTOM
-  (void)o; (void)draws; (void)n_draws; (void)d; (void)n_chains; (void)rng_state; (void)yrep;
-  return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive: generated models are not supported");
-#else
-  if (m->kind == EXMC_MODEL_CUSTOM || ic_n_data(m) < 0)
-    return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive: this model kind has no built-in datums");
-  if (!draws || !yrep || d != m->d || n_draws < 1 || n_chains < 1 || o.chain_lo < 0 || (o.resume && !rng_state))
-    return fail(EXMC_ERR_BADARG, "posterior predictive: bad arguments");
-  return EXMC_OK;
-#endif
-}
-
 int exmc_hip_posterior_predictive(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws_dev,
                                   int n_draws, int d, int n_chains, uint64_t* rng_state_dev, double* yrep_dev) {
-  int rc = predictive_check(m, o, draws_dev, n_draws, d, n_chains, rng_state_dev, yrep_dev);
+  int rc = pp_check(m, "posterior predictive", o, draws_dev, n_draws, d, n_chains,
+                    !yrep_dev || (o.resume && !rng_state_dev));
   if (rc) return rc;
 #ifndef EXMC_ONLY_CUSTOM
   HIP_TRY(hipSetDevice(m->device));
   PredictiveParams P;
-  P.draws = draws_dev;
+  pp_fill(P, m, o, draws_dev, n_draws, d, n_chains);
   P.yrep = yrep_dev;
   P.rng_state = rng_state_dev;
-  P.S = n_draws;
-  P.d = d;
-  P.C = n_chains;
-  P.N = ic_n_data(m);
-  P.chain_lo = o.chain_lo;
   P.resume = o.resume ? 1 : 0;
-  P.base_seed = o.seed;
-  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
-  P.nor_r = EXMC_NOR_R;
   rc = ic_with_src(m, [&](const auto& src) { return predictive_launch(m, src, P); });
 #endif
   return rc;
@@ -2665,74 +2672,44 @@ int exmc_hip_posterior_predictive(exmc_hip_model* m, exmc_hip_predictive_opts o,
 
 int exmc_hip_posterior_predictive_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws,
                                        int n_draws, int d, int n_chains, uint64_t* rng_state, double* yrep) {
-  int rc = predictive_check(m, o, draws, n_draws, d, n_chains, rng_state, yrep);
+  int rc = pp_check(m, "posterior predictive", o, draws, n_draws, d, n_chains, !yrep || (o.resume && !rng_state));
   if (rc) return rc;
 #ifndef EXMC_ONLY_CUSTOM
   HIP_TRY(hipSetDevice(m->device));
-  const size_t S = (size_t)n_draws, C = (size_t)n_chains, D = (size_t)d, N = (size_t)ic_n_data(m);
-  // scratch of the call: draws [S][d][C], yrep [S][N][C], the generators [2][C]
-  std::vector<double> h(S * D * C);
-  for (size_t c = 0; c < C; c++)
-    for (size_t s = 0; s < S; s++)
-      for (size_t j = 0; j < D; j++) h[(s * D + j) * C + c] = draws[(c * S + s) * D + j];
-  CallBuf buf;
-  rc = buf.alloc((S * D * C + S * N * C + 2 * C) * 8);
+  const size_t S = (size_t)n_draws, C = (size_t)n_chains, N = (size_t)ic_n_data(m);
+  Scratch sc;
+  const auto s_yrep = sc.take<double>(S * N * C);                // [S][N][C]
+  const auto s_rng = sc.take<uint64_t>(rng_state ? 2 * C : 0);   // the generators [2][C]
+  rc = sc.alloc_with_trace(draws, n_draws, d, n_chains);
   if (rc) return rc;
-  double* d_draws = buf.as<double>();
-  double* d_yrep = d_draws + S * D * C;
-  uint64_t* d_rng = (uint64_t*)(d_yrep + S * N * C);
-  HIP_TRY(hipMemcpy(d_draws, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-  if (rng_state && o.resume) HIP_TRY(hipMemcpy(d_rng, rng_state, 2 * C * 8, hipMemcpyHostToDevice));
-  rc = exmc_hip_posterior_predictive(m, o, d_draws, n_draws, d, n_chains, rng_state ? d_rng : nullptr, d_yrep);
+  if (rng_state && o.resume) HIP_TRY(hipMemcpy(sc.dev(s_rng), rng_state, 2 * C * 8, hipMemcpyHostToDevice));
+  rc = exmc_hip_posterior_predictive(m, o, sc.trace(), n_draws, d, n_chains, rng_state ? sc.dev(s_rng) : nullptr,
+                                     sc.dev(s_yrep));
+  if (!rc) rc = sc.download();
   if (rc) return rc;
-  h.resize(S * N * C);
-  HIP_TRY(hipMemcpy(h.data(), d_yrep, h.size() * 8, hipMemcpyDeviceToHost));
-  transpose_trace_vec(h.data(), yrep, n_draws, (int)N, n_chains);
-  if (rng_state) HIP_TRY(hipMemcpy(rng_state, d_rng, 2 * C * 8, hipMemcpyDeviceToHost));
+  transpose_trace_vec(sc.host(s_yrep), yrep, n_draws, (int)N, n_chains);
+  if (rng_state) std::copy(sc.host(s_rng), sc.host(s_rng) + 2 * C, rng_state);
 #endif
   return rc;
 }
 
 // ---- posterior predictive checks (include/exmc_hip_ppc.h; ppc_kernel, exmc_ppc.hpp) -------------------
-static int ppc_check(exmc_hip_model* m, const exmc_hip_predictive_opts& o, const void* draws, int n_draws, int d,
-                     int n_chains, bool outputs) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
-#ifdef EXMC_ONLY_CUSTOM
-  (void)o; (void)draws; (void)n_draws; (void)d; (void)n_chains; (void)outputs;
-  return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive checks: generated models are not supported");
-#else
-  if (m->kind == EXMC_MODEL_CUSTOM || ic_n_data(m) < 0)
-    return fail(EXMC_ERR_UNSUPPORTED, "posterior predictive checks: this model kind has no built-in datums");
-  if (!draws || !outputs || d != m->d || n_draws < 1 || n_chains < 1 || o.chain_lo < 0 || o.resume)
-    return fail(EXMC_ERR_BADARG, "posterior predictive checks: bad arguments");
-  return EXMC_OK;
-#endif
-}
-
 int exmc_hip_ppc(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws_dev, int n_draws, int d,
                  int n_chains, double* datum_sums_dev, int64_t* datum_counts_dev, int32_t* chain_counts_dev,
                  double* tstat_dev, double* t_obs, double* m0, double* y_obs) {
-  int rc = ppc_check(m, o, draws_dev, n_draws, d, n_chains,
-                     datum_sums_dev && datum_counts_dev && chain_counts_dev && t_obs && m0);
+  int rc = pp_check(m, "posterior predictive checks", o, draws_dev, n_draws, d, n_chains,
+                    !(datum_sums_dev && datum_counts_dev && chain_counts_dev && t_obs && m0) || o.resume);
   if (rc) return rc;
 #ifdef EXMC_ONLY_CUSTOM
   (void)tstat_dev; (void)y_obs;
 #else
   HIP_TRY(hipSetDevice(m->device));
   PpcParams P;
-  P.draws = draws_dev;
+  pp_fill(P, m, o, draws_dev, n_draws, d, n_chains);
   P.datum_sums = datum_sums_dev;
   P.datum_counts = (long long*)datum_counts_dev;
   P.chain_counts = (int*)chain_counts_dev;
   P.tstat = tstat_dev;
-  P.S = n_draws;
-  P.d = d;
-  P.C = n_chains;
-  P.N = ic_n_data(m);
-  P.chain_lo = o.chain_lo;
-  P.base_seed = o.seed;
-  P.zig_ki = zig_ki(m); P.zig_wi = zig_wi(m); P.zig_fi = zig_fi(m);
-  P.nor_r = EXMC_NOR_R;
   std::vector<double> y((size_t)P.N);
   rc = ic_with_src(m, [&](const auto& src) { return ppc_launch(m, src, P, y.data()); });
   if (rc) return rc;
@@ -2745,41 +2722,31 @@ int exmc_hip_ppc(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* dr
 
 int exmc_hip_ppc_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws, int n_draws, int d,
                       int n_chains, double* datum, double* t_obs, double* p_value, double* tstat) {
-  int rc = ppc_check(m, o, draws, n_draws, d, n_chains, datum && t_obs && p_value);
+  int rc = pp_check(m, "posterior predictive checks", o, draws, n_draws, d, n_chains,
+                    !(datum && t_obs && p_value) || o.resume);
   if (rc) return rc;
 #ifdef EXMC_ONLY_CUSTOM
   (void)tstat;
 #else
   HIP_TRY(hipSetDevice(m->device));
-  const size_t S = (size_t)n_draws, C = (size_t)n_chains, D = (size_t)d, N = (size_t)ic_n_data(m);
+  const size_t S = (size_t)n_draws, C = (size_t)n_chains, N = (size_t)ic_n_data(m);
   const size_t B = (C + kPpBlock - 1) / kPpBlock;
-  std::vector<double> h(S * D * C);
-  for (size_t c = 0; c < C; c++)
-    for (size_t s = 0; s < S; s++)
-      for (size_t j = 0; j < D; j++) h[(s * D + j) * C + c] = draws[(c * S + s) * D + j];
-  // scratch of the call: draws [S][d][C], sums [B][N][2], counts [B][N][2] (int64), tstat [S][4][C] where
-  // it is asked for, chain counts [4][C] (int32, last: the others stay 8-byte aligned)
-  const size_t n_ts = tstat ? S * kPpcStats * C : 0;
-  CallBuf buf;
-  rc = buf.alloc((S * D * C + 4 * B * N + n_ts) * 8 + kPpcStats * C * 4);
+  Scratch sc;
+  const auto s_sums = sc.take<double>(2 * B * N);                       // [B][N][2]
+  const auto s_counts = sc.take<int64_t>(2 * B * N);                    // [B][N][2]
+  const auto s_ts = sc.take<double>(tstat ? S * kPpcStats * C : 0);     // [S][4][C] where it is asked for
+  const auto s_cc = sc.take<int32_t>(kPpcStats * C);                    // [4][C]
+  rc = sc.alloc_with_trace(draws, n_draws, d, n_chains);
   if (rc) return rc;
-  double* d_draws = buf.as<double>();
-  double* d_sums = d_draws + S * D * C;
-  int64_t* d_counts = (int64_t*)(d_sums + 2 * B * N);
-  double* d_ts = (double*)(d_counts + 2 * B * N);
-  int32_t* d_cc = (int32_t*)(d_ts + n_ts);
-  HIP_TRY(hipMemcpy(d_draws, h.data(), h.size() * 8, hipMemcpyHostToDevice));
   std::vector<double> y(N);
   double m0 = 0.0;
-  rc = exmc_hip_ppc(m, o, d_draws, n_draws, d, n_chains, d_sums, d_counts, d_cc, tstat ? d_ts : nullptr, t_obs, &m0,
-                    y.data());
+  rc = exmc_hip_ppc(m, o, sc.trace(), n_draws, d, n_chains, sc.dev(s_sums), sc.dev(s_counts), sc.dev(s_cc),
+                    tstat ? sc.dev(s_ts) : nullptr, t_obs, &m0, y.data());
+  if (!rc) rc = sc.download();
   if (rc) return rc;
-  std::vector<double> sums(2 * B * N);
-  std::vector<int64_t> counts(2 * B * N);
-  std::vector<int32_t> cc(kPpcStats * C);
-  HIP_TRY(hipMemcpy(sums.data(), d_sums, sums.size() * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(counts.data(), d_counts, counts.size() * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(cc.data(), d_cc, cc.size() * 4, hipMemcpyDeviceToHost));
+  const double* sums = sc.host(s_sums);
+  const int64_t* counts = sc.host(s_counts);
+  const int32_t* cc = sc.host(s_cc);
   // the blocks left to right, then the finished numbers (include/exmc_hip_ppc.h)
   const double n = (double)(S * C);
   for (size_t i = 0; i < N; i++) {
@@ -2801,11 +2768,7 @@ int exmc_hip_ppc_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const doubl
     for (size_t c = 0; c < C; c++) above += cc[k * C + c];
     p_value[k] = (double)above / n;
   }
-  if (tstat) {
-    h.resize(n_ts);
-    HIP_TRY(hipMemcpy(h.data(), d_ts, n_ts * 8, hipMemcpyDeviceToHost));
-    transpose_trace_vec(h.data(), tstat, n_draws, kPpcStats, n_chains);
-  }
+  if (tstat) transpose_trace_vec(sc.host(s_ts), tstat, n_draws, kPpcStats, n_chains);
 #endif
   return rc;
 }

@@ -45,10 +45,7 @@ struct PathfinderParams {
   int32_t* num_iters;     // [C] or null: the path length, 1 + accepted steps
   int32_t* best_index;    // [C] or null: the path point of the best approximation (-1: none)
   int32_t* status;        // [C] or null: 1 when no path point has a finite ELBO
-  const uint64_t* zig_ki;
-  const double* zig_wi;
-  const double* zig_fi;
-  double nor_r;
+  RngArgs rng;
   FlatOrder flat;
 };
 
@@ -65,7 +62,7 @@ __global__ void __launch_bounds__(64) pathfinder_kernel(PathfinderParams P, type
   typename M::Lane ln;
   M::load(mc, l, ln);
   attach_scratch<M>(ln, xlds);
-  const ZigTables zt{P.zig_ki, P.zig_wi, P.zig_fi};
+  const ZigTables zt{P.rng.ki, P.rng.wi, P.rng.fi};
   const uint64_t seed = P.base_seed + 7919ULL * (uint64_t)(P.chain_lo + chain);
   const int hs = P.history_size;
 
@@ -87,7 +84,7 @@ __global__ void __launch_bounds__(64) pathfinder_kernel(PathfinderParams P, type
     Rng rng;
     rng_seed(rng, seed);
     for (int r = 0; r < D; r++) {
-      const double z = rng_normal(rng, zt, P.nor_r);
+      const double z = rng_normal(rng, zt, P.rng.nor_r);
 #pragma unroll
       for (int k = 0; k < DPL; k++)
         if (rank[k] == r) q[k] = z * 0.1;
@@ -240,7 +237,7 @@ __global__ void __launch_bounds__(64) pathfinder_kernel(PathfinderParams P, type
 #pragma unroll
     for (int k = 0; k < DPL; k++) dr[k] = 0.0;
     for (int r = 0; r < D; r++) {
-      const double z = rng_normal(rng, zt, P.nor_r);
+      const double z = rng_normal(rng, zt, P.rng.nor_r);
 #pragma unroll
       for (int k = 0; k < DPL; k++)
         if (rank[k] == r) dr[k] = best_mu[k] + best_sig[k] * z;

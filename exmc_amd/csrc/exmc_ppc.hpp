@@ -3,10 +3,9 @@
 // data set four test statistics against the observed ones (DESIGN.md "Posterior predictive checks"; C ABI
 // include/exmc_hip_ppc.h, which states the arithmetic).
 //
-// The skeleton and the replicates are predictive_kernel's (exmc_predictive.hpp): lane = chain, one
-// wavefront (one workgroup) per 64 consecutive chains, per draw the staged tile, Src::consts and
-// Src::prepare, per datum pp_load, Src::params and pp_sample on the chain's own generator, the ziggurat
-// tables in LDS. What a replicate goes into differs:
+// The walk over the trace and the replicates are predictive_kernel's, by the same calls (exmc_predictive.hpp,
+// "The walk": the LDS carve-up with tile2 at pp_behind, pp_seed, pp_stage; per datum pp_load, Src::params
+// and pp_sample on the chain's own generator). What a replicate goes into differs:
 //   - its chain's statistics of the draw (A, Bq, mn, mx): lane-local, the datums ascending;
 //   - its datum's running sums over chains and draws (E, E2, n_lt, n_eq): the transpose below.
 // The datums are walked in groups of 64. Draw phase: every lane with a chain draws the group's datums in
@@ -45,13 +44,10 @@ struct PpcParams {
   uint64_t base_seed;
   double m0;                 // the observed mean
   double t_obs[kPpcStats];   // the observed statistics: mean, var, min, max
-  const uint64_t* zig_ki;
-  const double* zig_wi;
-  const double* zig_fi;
-  double nor_r;
+  RngArgs rng;
 };
 
-// dynamic LDS: pp_lds_bytes(d) (the tile, the constants, the ziggurat tables), then tile2 [64][65]
+// dynamic LDS: pp_lds_bytes(d) (the tile, the constants, the ziggurat tables), then tile2 [64][65] at pp_behind
 __host__ __device__ inline size_t ppc_lds_bytes(int d) {
   return pp_lds_bytes(d) + (size_t)kPpBlock * kPpcStride * 8;
 }
@@ -65,46 +61,31 @@ __global__ __launch_bounds__(256) void ppc_obs_kernel(Src src, int N, double* __
 
 template <class Src>
 __global__ __launch_bounds__(kPpBlock) void ppc_kernel(Src src, PpcParams P) {
-  static_assert(kPpBlock == kIcTile, "one tile row per lane");
   extern __shared__ double ic_lds[];
   const int d = P.d, C = P.C, N = P.N;
-  const int ld = ic_ld(d);
-  double* tile = ic_lds;
-  double* cst = ic_lds + (size_t)kIcTile * ld;
-  const int tid = threadIdx.x;
-  const long long c0 = (long long)blockIdx.x * kPpBlock;
-  const long long c = c0 + tid;
+  const int tid = threadIdx.x, nrow = pp_rows(C);
+  const long long c = (long long)blockIdx.x * kPpBlock + tid;
   const bool live = c < C;
-  const int nrow = (int)((C - c0 < kPpBlock) ? C - c0 : kPpBlock);   // rows of the tiles that hold a chain
-  double* lz = cst + (size_t)kIcTile * (kIcConsts + 1);
-  double* tile2 = lz + 3 * 256;
+  double* const tile2 = pp_behind(ic_lds, d);
+  double* lz = pp_tables_at(ic_lds, d);
   for (int i = tid; i < 256; i += kPpBlock) {
-    lz[i] = __longlong_as_double((long long)P.zig_ki[i]);
-    lz[256 + i] = P.zig_wi[i];
-    lz[512 + i] = P.zig_fi[i];
+    lz[i] = __longlong_as_double((long long)P.rng.ki[i]);
+    lz[256 + i] = P.rng.wi[i];
+    lz[512 + i] = P.rng.fi[i];
   }
-  const ZigTables zt{(const uint64_t*)lz, lz + 256, lz + 512};   // (read after the loop's first barrier)
+  const ZigTables zt{(const uint64_t*)lz, lz + 256, lz + 512};   // (read after pp_stage's first barrier)
   Rng rng{0, 0};
-  if (live) rng_seed(rng, P.base_seed + 7919ULL * (uint64_t)(P.chain_lo + c));
-  const PpRng g{rng, zt, P.nor_r};
-  double* q = tile + (size_t)tid * ld;
-  double* cq = cst + tid * (kIcConsts + 1) + 1;
+  pp_seed(rng, c, C, P.base_seed, P.chain_lo, false, nullptr);
+  const PpRng g{rng, zt, P.rng.nor_r};
+  const double* q = pp_tile_row(ic_lds, d, tid);
+  const double* cq = pp_const_row(ic_lds, d, tid);
   const double Nd = (double)N, m0 = P.m0;
   int cnt[kPpcStats] = {0, 0, 0, 0};
   // the block's slots of the per-datum outputs: [N][2] each
   double* bsum = P.datum_sums + (size_t)blockIdx.x * N * 2;
   long long* bcnt = P.datum_counts + (size_t)blockIdx.x * N * 2;
   for (int s = 0; s < P.S; s++) {
-    __syncthreads();   // the previous draw's tile has been read
-    for (int e = tid; e < kIcTile * d; e += kPpBlock) {
-      const int j = e / kIcTile, t = e - j * kIcTile;
-      tile[(size_t)t * ld + j] = (t < nrow) ? P.draws[((size_t)s * d + j) * C + (c0 + t)] : 0.0;
-    }
-    __syncthreads();
-    src.consts(q, cq);
-    __syncthreads();
-    src.prepare(tile, cst, ld, kIcTile, tid, kPpBlock);
-    __syncthreads();
+    pp_stage(src, ic_lds, P.draws, s, d, C);
     double A = 0.0, Bq = 0.0, mn = __builtin_inf(), mx = -__builtin_inf();
     typename Src::Datum dat{};
     for (int i0 = 0; i0 < N; i0 += kPpBlock) {

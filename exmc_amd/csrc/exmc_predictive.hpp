@@ -3,7 +3,8 @@
 // "Posterior predictive"; C ABI include/exmc_hip_predictive.h).
 //
 // One lane owns one chain and its generator; one wavefront (one workgroup) owns 64 consecutive chains.
-// Nothing is summed across lanes, so a chain's replicates do not depend on the launch shape. Per draw s:
+// Nothing is summed across lanes, so a chain's replicates do not depend on the launch shape. Per draw s
+// (steps 1 and 2 are pp_stage, which ppc_kernel of exmc_ppc.hpp calls too):
 //   1. stage: the 64 chains' rows of draw s into the LDS tile [64][ic_ld(d)] (coalesced over chains): 64
 //      consecutive pooled samples of one draw, the tile the sources of exmc_ic.hpp take;
 //   2. Src::consts, one lane per row, then Src::prepare with the wave as the cooperating group (radon's
@@ -36,10 +37,7 @@ struct PredictiveParams {
   int S, d, C, N;
   int chain_lo, resume;
   uint64_t base_seed;
-  const uint64_t* zig_ki;
-  const double* zig_wi;
-  const double* zig_fi;
-  double nor_r;
+  RngArgs rng;
 };
 
 struct PpRng {
@@ -111,50 +109,80 @@ __device__ __forceinline__ IcRadonSrc::Datum pp_load(const IcRadonSrc& src, int 
 // dynamic LDS: the tile and the constants of ic_lds_bytes(d), then the ziggurat tables ki, wi, fi [256] each
 __host__ __device__ inline size_t pp_lds_bytes(int d) { return ic_lds_bytes(d) + (size_t)3 * 256 * 8; }
 
+// The walk over a device trace that predictive_kernel and ppc_kernel (exmc_ppc.hpp) share: lane = chain,
+// one wavefront per 64 consecutive chains. The LDS is carved by pp_tile_row / pp_const_row / pp_tables_at /
+// pp_behind, pp_seed gives the lane its chain's generator and pp_stage readies draw s; what a kernel does
+// with the replicates pp_sample(src.params(dat, q, cq), g) of the staged draw is its own. (Plain values, no
+// walk object, and the table copy written out in both: DESIGN.md, profiles/fit_pp_refactor, for why.)
+__device__ __forceinline__ double* pp_consts_at(double* lds, int d) { return lds + (size_t)kIcTile * ic_ld(d); }
+__device__ __forceinline__ double* pp_tables_at(double* lds, int d) {
+  return pp_consts_at(lds, d) + (size_t)kIcTile * (kIcConsts + 1);
+}
+__device__ __forceinline__ double* pp_behind(double* lds, int d) { return pp_tables_at(lds, d) + 3 * 256; }
+// row `t` of the tile [64][ic_ld(d)] and of the constants [64][kIcConsts + 1]
+__device__ __forceinline__ double* pp_tile_row(double* lds, int d, int t) { return lds + (size_t)t * ic_ld(d); }
+__device__ __forceinline__ double* pp_const_row(double* lds, int d, int t) {
+  return pp_consts_at(lds, d) + t * (kIcConsts + 1) + 1;
+}
+__device__ __forceinline__ int pp_rows(int C) {   // rows of the workgroup's tile that hold a chain
+  const long long c0 = (long long)blockIdx.x * kPpBlock;
+  return (int)((C - c0 < kPpBlock) ? C - c0 : kPpBlock);
+}
+
+// the generator of chain chain_lo + c (c < C), or with `resume` the one a call before left in state [2][C]
+__device__ __forceinline__ void pp_seed(Rng& rng, long long c, int C, uint64_t base_seed, int chain_lo, bool resume,
+                                        const uint64_t* state) {
+  if (c < C) {
+    if (resume) {
+      rng.a = state[c];
+      rng.b = state[(size_t)C + c];
+    } else {
+      rng_seed(rng, base_seed + 7919ULL * (uint64_t)(chain_lo + c));
+    }
+  }
+}
+
+// draw s of draws [S][d][C] into the tile, Src::consts and Src::prepare; every lane of the workgroup
+// calls it for every draw (four barriers)
+template <class Src>
+__device__ __forceinline__ void pp_stage(const Src& src, double* lds, const double* draws, int s, int d, int C) {
+  static_assert(kPpBlock == kIcTile, "one tile row per lane");
+  const int ld = ic_ld(d), tid = threadIdx.x, nrow = pp_rows(C);
+  const long long c0 = (long long)blockIdx.x * kPpBlock;
+  __syncthreads();   // the previous draw's tile has been read
+  for (int e = tid; e < kIcTile * d; e += kPpBlock) {
+    const int j = e / kIcTile, t = e - j * kIcTile;
+    lds[(size_t)t * ld + j] = (t < nrow) ? draws[((size_t)s * d + j) * C + (c0 + t)] : 0.0;
+  }
+  __syncthreads();
+  src.consts(pp_tile_row(lds, d, tid), pp_const_row(lds, d, tid));
+  __syncthreads();
+  src.prepare(lds, pp_consts_at(lds, d), ld, kIcTile, tid, kPpBlock);
+  __syncthreads();
+}
+
 template <class Src>
 __global__ __launch_bounds__(kPpBlock) void predictive_kernel(Src src, PredictiveParams P) {
-  static_assert(kPpBlock == kIcTile, "one tile row per lane");
   extern __shared__ double ic_lds[];
   const int d = P.d, C = P.C, N = P.N;
-  const int ld = ic_ld(d);
-  double* tile = ic_lds;
-  double* cst = ic_lds + (size_t)kIcTile * ld;
   const int tid = threadIdx.x;
-  const long long c0 = (long long)blockIdx.x * kPpBlock;
-  const long long c = c0 + tid;
+  const long long c = (long long)blockIdx.x * kPpBlock + tid;
   const bool live = c < C;
-  const int nrow = (int)((C - c0 < kPpBlock) ? C - c0 : kPpBlock);   // rows of the tile that hold a chain
-  double* lz = cst + (size_t)kIcTile * (kIcConsts + 1);
+  double* lz = pp_tables_at(ic_lds, d);
   for (int i = tid; i < 256; i += kPpBlock) {
-    lz[i] = __longlong_as_double((long long)P.zig_ki[i]);
-    lz[256 + i] = P.zig_wi[i];
-    lz[512 + i] = P.zig_fi[i];
+    lz[i] = __longlong_as_double((long long)P.rng.ki[i]);
+    lz[256 + i] = P.rng.wi[i];
+    lz[512 + i] = P.rng.fi[i];
   }
-  const ZigTables zt{(const uint64_t*)lz, lz + 256, lz + 512};   // (read after the loop's first barrier)
+  const ZigTables zt{(const uint64_t*)lz, lz + 256, lz + 512};   // (read after pp_stage's first barrier)
   Rng rng{0, 0};
-  if (live) {
-    if (P.resume) {
-      rng.a = P.rng_state[c];
-      rng.b = P.rng_state[(size_t)C + c];
-    } else {
-      rng_seed(rng, P.base_seed + 7919ULL * (uint64_t)(P.chain_lo + c));
-    }
-  }
-  const PpRng g{rng, zt, P.nor_r};
-  double* q = tile + (size_t)tid * ld;
-  double* cq = cst + tid * (kIcConsts + 1) + 1;
+  pp_seed(rng, c, C, P.base_seed, P.chain_lo, P.resume, P.rng_state);
+  const PpRng g{rng, zt, P.rng.nor_r};
+  const double* q = pp_tile_row(ic_lds, d, tid);
+  const double* cq = pp_const_row(ic_lds, d, tid);
   for (int s = 0; s < P.S; s++) {
-    __syncthreads();   // the previous draw's tile has been read
-    for (int e = tid; e < kIcTile * d; e += kPpBlock) {
-      const int j = e / kIcTile, t = e - j * kIcTile;
-      tile[(size_t)t * ld + j] = (t < nrow) ? P.draws[((size_t)s * d + j) * C + (c0 + t)] : 0.0;
-    }
-    __syncthreads();
-    src.consts(q, cq);
-    __syncthreads();
-    src.prepare(tile, cst, ld, kIcTile, tid, kPpBlock);
-    __syncthreads();
-    if (!live) continue;
+    pp_stage(src, ic_lds, P.draws, s, d, C);
+    if (!live) continue;   // after the draw's last barrier
     double* out = P.yrep + (size_t)s * N * C + c;
     typename Src::Datum dat{};
     for (int i = 0; i < N; i++) {
