@@ -57,12 +57,12 @@ hipError_t print_sections(const char* what, double ms) {
   e = hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z));
   if (e != hipSuccess) return e;
   static const char* nm[9] = {"transition_start", "doubling_start", "leapfrog+model", "leaf",
-                              "ascend", "outer_merge", "transition_done", "", "loop"};
+                              "ascend", "outer_merge", "transition_done", "tree_prefix", "loop"};
   unsigned long long tot = 0;
   for (int i = 0; i < 9; i++) tot += h[i];
   fprintf(stderr, "[exmc prof] %s %.3f ms, passes (sum over waves) %llu, cycles %llu\n", what, ms, h[9], tot);
   for (int i = 0; i < 9; i++)
-    if (i != 7 && h[9])
+    if ((i != 7 || h[7]) && h[9])   // tree_prefix: once per transition, outside the passes (M::kTreePrefix)
       fprintf(stderr, "[exmc prof]   %-18s %6.1f%%  %8.1f cycles/pass\n", nm[i],
               100.0 * (double)h[i] / (double)tot, (double)h[i] / (double)h[9]);
   if (h[10])

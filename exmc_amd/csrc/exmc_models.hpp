@@ -97,6 +97,11 @@ struct ModelDefaults {
   // the log_ge1 of its log_sum_exp as one main path with two fix-ups.
   static constexpr bool kPassExpPairs = false;
   static constexpr bool kOuterLogPair = false;
+  // The one-wave leaf-pair form runs doublings 0, 1 and 2 of a transition as one straight-line unit:
+  // seven leapfrogs back to back, then the tree's own exponentials and logarithms of all three
+  // doublings in six lane-batched evaluations (exmc_nuts.hpp tree_prefix); same bits. Needs
+  // kLeafPairs and 11 lanes a group.
+  static constexpr bool kTreePrefix = false;
 };
 
 // the dynamic LDS of the running kernel (every extern __shared__ array names the same base)
@@ -144,6 +149,8 @@ struct EightSchools : ModelDefaults {
   static constexpr bool kLeafPairExp = (G == 16);
   static constexpr bool kLeanMomentum = (G == 16);
   static constexpr bool kOuterLogPair = (G == 16);
+  // doublings 0-2 of every tree as one straight-line unit ("Round 9")
+  static constexpr bool kTreePrefix = (G == 16);
   using MM = Math<kVregMath>;
   using Consts = EightSchoolsConsts;
   struct Lane {
@@ -1704,6 +1711,7 @@ struct RowDenseModel : M {
   static constexpr bool kPipeWarmup = false;   // the dense warmup is the one-wave form
   // the outer merge's log pair is measured, and switched on, for the diagonal-mass kernel only
   static constexpr bool kOuterLogPair = false;
+  static constexpr bool kTreePrefix = false;   // likewise (exmc_nuts.hpp tree_prefix)
   static_assert(M::DPL == 1 && M::D <= 12, "row layout: one dimension per lane, D <= 12");
 };
 

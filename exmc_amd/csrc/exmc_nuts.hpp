@@ -833,12 +833,20 @@ __device__ __forceinline__ void draw_momentum(const NutsLane<M, G>& L, Rng& rng,
 // ------------------------------------------------------------------------------------------
 struct NoPipe {
   static constexpr bool kOn = false;
-  static constexpr bool kLeafPairs = true;   // nuts_run may walk leaf pairs itself (M::kLeafPairs)
+  static constexpr bool kLeafPairs = true;    // nuts_run may walk leaf pairs itself (M::kLeafPairs)
+  static constexpr bool kTreePrefix = true;   // ... and doublings 0-2 as one unit (M::kTreePrefix)
+};
+// one wave, leaf pairs where the model has them, every doubling through the walk
+struct NoPipeWalk {
+  static constexpr bool kOn = false;
+  static constexpr bool kLeafPairs = true;
+  static constexpr bool kTreePrefix = false;
 };
 // one wave, a pass per leaf whatever the model's traits say
 struct NoPipeLeaf {
   static constexpr bool kOn = false;
   static constexpr bool kLeafPairs = false;
+  static constexpr bool kTreePrefix = false;
 };
 
 // a finished subtree as the tree wave continues with it (nuts_run's c_* variables)
@@ -862,6 +870,7 @@ template <int DPL>
 struct PipeBox {
   static constexpr bool kOn = true;
   static constexpr bool kLeafPairs = false;
+  static constexpr bool kTreePrefix = false;
   static constexpr int kQuit = 4 * DPL + 4;   // start row: the tree wave abandons the kernel
   static constexpr int kCtrl = 4 * DPL + 5;
   static constexpr int kSlot = kCtrl + 4;
@@ -975,12 +984,17 @@ struct PairPick {
   __device__ __forceinline__ double operator()(MM, double x, double) const { return MM::exp_le0(x); }
 };
 
-template <class M, int G, class Lse = PairLse, class Pick = PairPick>
+// draw(trng): the uniform of the pair's proposal, for a caller that has read it ahead (tree_prefix)
+struct PairDraw {
+  __device__ __forceinline__ double operator()(Rng& r) const { return rng_uniform(r); }
+};
+
+template <class M, int G, class Lse = PairLse, class Pick = PairPick, class Draw = PairDraw>
 __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const PipeLeaf<M::DPL>& a,
                                                const PipeLeaf<M::DPL>& b, bool pair,
                                                const double (&q0)[M::DPL], const double (&g0)[M::DPL],
                                                Rng& trng, PipeUnit<M::DPL>& u, Lse&& lse = Lse{},
-                                               Pick&& pick = Pick{}) {
+                                               Pick&& pick = Pick{}, Draw&& draw = Draw{}) {
   constexpr int DPL = M::DPL;
   using MM = Math<M::kVregMath>;
 #pragma unroll
@@ -998,7 +1012,7 @@ __device__ __forceinline__ void pipe_pair_unit(const NutsLane<M, G>& L, const Pi
   u.turn = false;
   if (pair && !a.div) {
     const double lsw = lse(MM{}, a.lsw, b.lsw);
-    const double uu = rng_uniform(trng);
+    const double uu = draw(trng);
     const bool use_b = uu < pick(MM{}, b.lsw - lsw, lsw);   // lsw >= b.lsw
     bool turning = b.div;
     if (!turning) {
@@ -1226,6 +1240,250 @@ __device__ __forceinline__ bool pipe_integrate_transition(const typename M::Cons
   return true;
 }
 
+// The trajectory nuts_run keeps between doublings (its t_* variables, the two endpoints and the
+// stop flag), for tree_prefix
+template <int DPL>
+struct TreeTop {
+  double (&qL)[DPL], (&pL)[DPL], (&gL)[DPL], (&qR)[DPL], (&pR)[DPL], (&gR)[DPL];
+  double (&rho)[DPL], (&qp)[DPL], (&gp)[DPL];
+  double &logpP, &lsw, &acc;
+  int &n, &depth;
+  bool &div, &turn, &alive;
+};
+
+// Doublings 0, 1 and 2 of a transition as one straight-line unit (M::kTreePrefix; the one-wave
+// leaf-pair form). Nearly every tree runs exactly these three doublings, and once their seven
+// leapfrogs are integrated every argument of the tree's own exponentials and logarithms depends on
+// the seven energy errors and on uniforms only -- which are known in advance, the tree's generator
+// being a private copy. So: the seven leapfrogs back to back (leaf k + 1 of a doubling starts from
+// leaf k, a doubling from the endpoint its direction selects: a leaf already integrated, or the
+// start), the leaves' scalars, and then six lane-batched evaluations instead of nineteen:
+//   1 exp  the 7 accept statistics, the 3 pairs' log_sum_exp, doubling 0's outer log_sum_exp
+//   2 log  the 3 pairs' log_ge1, doubling 0's outer log_ge1, log_unit of every uniform an outer merge
+//          can draw (which one it is depends on where a subtree ended: 1, 2 and 4 candidates)
+//   3 exp  the 3 pairs' proposal weights, the level-1 merge's and doubling 1's outer log_sum_exp
+//   4 log  the level-1 merge's and doubling 1's outer log_ge1
+//   5 exp  the level-1 merge's proposal weight, doubling 2's outer log_sum_exp
+//   6 log  doubling 2's outer log_ge1
+// Each value comes from the function that computes it in the walk (exp_le0, lse_arg / lse_finish,
+// log_main with its fix-ups), the merges run in the walk's order -- pair units, the level-1 merge,
+// the three outer merges -- and take their uniforms in the walk's order: u[0] direction, u[1] outer
+// merge; u[2] direction, u[3] pair, u[4] outer; u[5] direction, u[6] pair, u[7] pair, u[8] level-1
+// merge, u[9] outer, each moving up by one for a pair whose first leaf diverged (no draw) and the
+// outer merge of doubling 2 taking u[6] or u[7] when its first pair came back unmerged, diverged
+// or turning (tree.ex:1175-1177). A group whose tree has ended is masked from there on and keeps
+// integrating its own trajectory as scratch. On return T is what the walk's doubling loop holds
+// before depth 3 and trng stands behind the ten uniforms (a group that stopped drew fewer; its copy
+// is discarded). (q, p, g): left at the last leaf, the scratch state an idle group goes on with.
+template <class M, int G>
+__device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const NutsLane<M, G>& L,
+                                            double eps, double jlp0, int max_depth, Rng& trng,
+                                            TreeTop<M::DPL> T, double (&q)[M::DPL], double (&p)[M::DPL],
+                                            double (&g)[M::DPL]) {
+  constexpr int DPL = M::DPL;
+  using MM = Math<M::kVregMath>;
+  static_assert(G >= 11, "one lane per argument of the widest batch");
+  static_assert(!M::kRegradProposal, "the proposal's gradient travels with it");
+  double u[10];
+#pragma unroll
+  for (int i = 0; i < 10; i++) u[i] = rng_uniform(trng);
+  const bool r0 = u[0] > 0.5, r1 = u[2] > 0.5, r2 = u[5] > 0.5;   // tree.ex:403
+
+  // ---- the seven leapfrogs (batched_leapfrog.ex:79-85), as leaf_pair integrates them ----
+  PipeLeaf<DPL> f0, f1, f2, f3, f4, f5, f6;
+  auto leap = [&](double eps_dir, PipeLeaf<DPL>& lf) {
+    const double h = eps_dir / 2.0;
+#pragma unroll
+    for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
+    mass_drift<M, G>(L, eps_dir, p, q);
+    lf.logp = M::logp_grad(mc, L.ln, L.l, q, g);
+#pragma unroll
+    for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) { lf.q[k] = q[k]; lf.p[k] = p[k]; lf.g[k] = g[k]; }
+  };
+  double q1[DPL], g1[DPL], q2[DPL], g2[DPL];   // where doublings 1 and 2 start
+#pragma unroll
+  for (int k = 0; k < DPL; k++) { q[k] = T.qL[k]; p[k] = T.pL[k]; g[k] = T.gL[k]; }
+  leap(r0 ? eps : -eps, f0);
+  // doubling 1 leaves from leaf 0 where it goes doubling 0's way, else from the start
+  const bool same01 = (r0 == r1), same12 = (r1 == r2);
+#pragma unroll
+  for (int k = 0; k < DPL; k++) {
+    q[k] = q1[k] = same01 ? f0.q[k] : T.qL[k];
+    p[k] = same01 ? f0.p[k] : T.pL[k];
+    g[k] = g1[k] = same01 ? f0.g[k] : T.gL[k];
+  }
+  leap(r1 ? eps : -eps, f1);
+  leap(r1 ? eps : -eps, f2);
+  // doubling 2 from leaf 2, or from the other endpoint: leaf 0 if doubling 1 went the other way, else the start
+#pragma unroll
+  for (int k = 0; k < DPL; k++) {
+    q[k] = q2[k] = same12 ? f2.q[k] : (same01 ? T.qL[k] : f0.q[k]);
+    p[k] = same12 ? f2.p[k] : (same01 ? T.pL[k] : f0.p[k]);
+    g[k] = g2[k] = same12 ? f2.g[k] : (same01 ? T.gL[k] : f0.g[k]);
+  }
+  leap(r2 ? eps : -eps, f3);
+  leap(r2 ? eps : -eps, f4);
+  leap(r2 ? eps : -eps, f5);
+  leap(r2 ? eps : -eps, f6);
+
+  // ---- the leaves' scalars (tree.ex:1042-1048 without a branch, see leaf_pair) and batch 1 ----
+  auto scalars = [&](PipeLeaf<DPL>& lf) -> double {
+    const double jlp = lf.logp - mass_ke<M, G>(L, lf.p);
+    const bool fin = exmc_isfinite(jlp);
+    const double dl = jlp - jlp0;
+    lf.div = fin ? (dl < -1000.0) : true;
+    lf.lsw = fin ? dl : -1001.0;
+    return fmin(dl, 0.0);
+  };
+  double x[11];
+  x[0] = scalars(f0); x[1] = scalars(f1); x[2] = scalars(f2); x[3] = scalars(f3);
+  x[4] = scalars(f4); x[5] = scalars(f5); x[6] = scalars(f6);
+  x[7] = MM::lse_arg(f1.lsw, f2.lsw);
+  x[8] = MM::lse_arg(f3.lsw, f4.lsw);
+  x[9] = MM::lse_arg(f5.lsw, f6.lsw);
+  x[10] = MM::lse_arg(T.lsw, f0.lsw);
+  lane_batch<G>(x, L.l, [](double v) { return MM::exp_le0(v); });
+  auto accept = [&](PipeLeaf<DPL>& lf, double ex) { lf.acc = lf.div ? 0.0 : fmin(1.0, ex); };
+  accept(f0, x[0]); accept(f1, x[1]); accept(f2, x[2]); accept(f3, x[3]);
+  accept(f4, x[4]); accept(f5, x[5]); accept(f6, x[6]);
+
+  // ---- batch 2 ----
+  double y[11] = {1.0 + x[7], 1.0 + x[8], 1.0 + x[9], 1.0 + x[10], u[1], u[3], u[4], u[6], u[7], u[8], u[9]};
+  {
+    double v[11];
+#pragma unroll
+    for (int i = 0; i < 11; i++) v[i] = y[i];
+    lane_batch<G>(y, L.l, [](double a) { return MM::log_main(a); });
+#pragma unroll
+    for (int i = 0; i < 4; i++) y[i] = exmc_log_ge1_fix(v[i], y[i]);
+#pragma unroll
+    for (int i = 4; i < 11; i++) y[i] = exmc_log_unit_fix(v[i], y[i]);
+  }
+  const double lsw12 = MM::lse_finish(f1.lsw, f2.lsw, y[0]);
+  const double lsw34 = MM::lse_finish(f3.lsw, f4.lsw, y[1]);
+  const double lsw56 = MM::lse_finish(f5.lsw, f6.lsw, y[2]);
+  // the lsw a pair's unit carries: a diverged first leaf travels alone (pipe_pair_unit)
+  const double c12 = f1.div ? f1.lsw : lsw12;
+  const double c34 = f3.div ? f3.lsw : lsw34;
+  const double c56 = f5.div ? f5.lsw : lsw56;
+
+  // merge_trajectories (tree.ex:1479-1568) of subtree c, as nuts_run's outer merge performs it
+  auto outer = [&](const PipeUnit<DPL>& c, bool go_right, double log1pe, double logu, int depth) {
+    if (!T.alive) return;
+    const double lsw = MM::lse_finish(T.lsw, c.lsw, log1pe);
+    const bool use_sub = logu < (c.lsw - T.lsw);
+    if (use_sub) {
+      T.logpP = c.logpP;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) { T.qp[k] = c.qp[k]; T.gp[k] = c.gp[k]; }
+    }
+    const bool divg = T.div || c.div;
+    bool turning = divg || c.turn;
+    double rho[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) rho[k] = T.rho[k] + c.rho[k];
+    if (!turning) {
+      double nearp[DPL], farp[DPL], s2[DPL], s3[DPL];
+#pragma unroll
+      for (int k = 0; k < DPL; k++) {
+        nearp[k] = go_right ? T.pR[k] : T.pL[k];
+        farp[k] = go_right ? T.pL[k] : T.pR[k];
+        s2[k] = T.rho[k] + c.pin[k];
+        s3[k] = nearp[k] + c.rho[k];
+      }
+      bool c1, c23;
+      mass_uturn3<M, G>(L, rho, farp, c.p, s2, farp, c.pin, s3, nearp, c.p, c1, c23);
+      turning = c1 || c23;
+    }
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      T.rho[k] = rho[k];
+      if (go_right) { T.qR[k] = c.q[k]; T.pR[k] = c.p[k]; T.gR[k] = c.g[k]; }
+      else { T.qL[k] = c.q[k]; T.pL[k] = c.p[k]; T.gL[k] = c.g[k]; }
+    }
+    T.lsw = lsw;
+    T.n += c.n;
+    T.acc = T.acc + c.acc;
+    T.div = divg;
+    T.turn = turning;
+    T.depth = depth + 1;
+    // tree.ex:1607-1618: the trajectory stops at max depth, on divergence or on a U-turn
+    T.alive = !(T.depth >= max_depth || T.div || T.turn);
+  };
+
+  // ---- doubling 0: the lone leaf ----
+  double s0q[DPL], s0g[DPL];
+#pragma unroll
+  for (int k = 0; k < DPL; k++) { s0q[k] = T.qL[k]; s0g[k] = T.gL[k]; }
+  PipeUnit<DPL> c;
+  pipe_pair_unit<M, G>(L, f0, f0, false, s0q, s0g, trng, c);
+  outer(c, r0, y[3], y[4], 0);
+
+  // ---- batch 3 (T.lsw: the trajectory's after doubling 0) and the pair units ----
+  double w[5] = {f2.lsw - lsw12, f4.lsw - lsw34, f6.lsw - lsw56, MM::lse_arg(lsw34, c56), MM::lse_arg(T.lsw, c12)};
+  lane_batch<G>(w, L.l, [](double v) { return MM::exp_le0(v); });
+  PipeUnit<DPL> c1, ca, cb;
+  pipe_pair_unit<M, G>(L, f1, f2, true, q1, g1, trng, c1, [&](auto, double, double) { return lsw12; },
+                       [&](auto, double, double) { return w[0]; }, [&](Rng&) { return u[3]; });
+  pipe_pair_unit<M, G>(L, f3, f4, true, q2, g2, trng, ca, [&](auto, double, double) { return lsw34; },
+                       [&](auto, double, double) { return w[1]; }, [&](Rng&) { return u[6]; });
+  pipe_pair_unit<M, G>(L, f5, f6, true, f4.q, f4.g, trng, cb, [&](auto, double, double) { return lsw56; },
+                       [&](auto, double, double) { return w[2]; }, [&](Rng&) { return u[7]; });
+  // doubling 2's first pair parks and waits for the second unless it diverged or turned
+  const bool parked = !(ca.div || ca.turn);
+
+  // ---- batch 4, doubling 1's outer merge ----
+  double z[2] = {1.0 + w[3], 1.0 + w[4]};
+  {
+    const double v0 = z[0], v1 = z[1];
+    lane_batch<G>(z, L.l, [](double a) { return MM::log_main(a); });
+    z[0] = exmc_log_ge1_fix(v0, z[0]);
+    z[1] = exmc_log_ge1_fix(v1, z[1]);
+  }
+  const double lsw_m = MM::lse_finish(lsw34, c56, z[0]);
+  outer(c1, r1, z[1], f1.div ? y[5] : y[6], 1);
+
+  // ---- batch 5; the level-1 merge of doubling 2 (tree.ex:1390-1476), as nuts_run's ascent ----
+  double e[2] = {c56 - lsw_m, MM::lse_arg(T.lsw, parked ? lsw_m : c34)};
+  lane_batch<G>(e, L.l, [](double v) { return MM::exp_le0(v); });
+  if (parked) {
+    const double um = f5.div ? u[7] : u[8];
+    const bool use_b = um < e[0];
+    if (!use_b) {
+      cb.logpP = ca.logpP;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) { cb.qp[k] = ca.qp[k]; cb.gp[k] = ca.gp[k]; }
+    }
+    bool turning = cb.div || cb.turn;
+    if (!turning) {
+      double rho[DPL], s2[DPL], s3[DPL];
+#pragma unroll
+      for (int k = 0; k < DPL; k++) {
+        rho[k] = ca.rho[k] + cb.rho[k];
+        s2[k] = ca.rho[k] + cb.pin[k];
+        s3[k] = ca.p[k] + cb.rho[k];
+      }
+      bool t1, t23;
+      mass_uturn3<M, G>(L, rho, ca.pin, cb.p, s2, ca.pin, cb.pin, s3, ca.p, cb.p, t1, t23);
+      turning = t1 || t23;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) { cb.rho[k] = rho[k]; cb.pin[k] = ca.pin[k]; }
+    }
+    cb.lsw = lsw_m;
+    cb.acc = ca.acc + cb.acc;
+    cb.n = 2 + cb.n;
+    cb.turn = turning;
+  } else {
+    cb = ca;
+  }
+
+  // ---- batch 6, doubling 2's outer merge ----
+  const double lu2 = f3.div ? y[7] : (!parked ? y[8] : (f5.div ? y[9] : y[10]));
+  outer(cb, r2, MM::log_ge1(1.0 + e[1]), lu2, 2);
+}
+
 // n_draws NUTS transitions of this group's chain. sink(draw, q, logp, depth, n_steps, divergent,
 // accept_sum, jlp0) is called once per finished transition.
 // stack slots of one pending node: rho, p_in, p_out, q_prop, g_prop (DPL each), lsw, logp_prop, acc
@@ -1238,6 +1496,12 @@ __device__ __forceinline__ bool pipe_integrate_transition(const typename M::Cons
 // tree.ex:1175-1177 path, handled by the same level loop) idles until the deepest tree of the
 // wavefront is finished: for eight_schools E[max of 4 trees] / E[tree] = 1.18 extra passes buy a
 // pass that costs ~0.6x of the asynchronous one (no union of divergent paths, no exec juggling).
+// Where the model says so (M::kTreePrefix, the one-wave leaf-pair form) the skeleton's first three
+// doublings are not walked at all: tree_prefix runs them straight-line for all four groups, a group
+// that stops inside them masked from there on, and the doubling loop below starts at depth 3 with
+// the trajectory, the endpoints, the stop flags and the tree's generator as the walk would have
+// left them. For eight_schools 85 % of a wavefront's transitions end there (DESIGN.md section 5,
+// "Round 9").
 // idle(): work of the caller that does not depend on this transition's outcome; called once per
 // transition where the pipelined tree wave would otherwise wait for the first leaf.
 struct NoIdle {
@@ -1323,7 +1587,17 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
     idle();
     EXMC_PROF(0)
 
-    for (int depth = 0; Pipe::kOn || __any(alive ? 1 : 0) != 0; depth++) {   // depth is wave-uniform
+    // M::kTreePrefix: doublings 0-2 straight-line (tree_prefix), the walk below from depth 3 on
+    constexpr bool kPrefix = M::kTreePrefix && M::kLeafPairs && Pipe::kTreePrefix && EXMC_ABLATE == 0;
+    if constexpr (kPrefix) {
+      tree_prefix<M, G>(mc, L, eps, jlp0, max_depth, trng,
+                        TreeTop<DPL>{qL, pL, gL, qR, pR, gR, t_rho, t_qp, t_gp, t_logpP, t_lsw, t_acc,
+                                     t_n, t_depth, t_div, t_turn, alive},
+                        q, p, g);
+      EXMC_PROF(7)
+    }
+
+    for (int depth = kPrefix ? 3 : 0; Pipe::kOn || __any(alive ? 1 : 0) != 0; depth++) {   // depth is wave-uniform
       if (alive) {
         // tree.ex:403-413 direction + outward endpoint
         const double u = rng_uniform(trng);
@@ -2884,7 +3158,7 @@ __global__ void __launch_bounds__(kNutsBlock, M::kNutsWavesPerSimd) indep_kernel
       // sampler.ex:709: depth cap 8 for absolute warmup index < 200, Phase II only
       const int cap = (in_window && i < 200) ? (P.max_depth < 8 ? P.max_depth : 8) : P.max_depth;
       auto idle = [&]() { da.prepare(); };
-      nuts_run<M, G, LDSL>(mc, L, st, 1, exmc_exp(da.log_epsilon), cap, wsink, (NoPipe*)nullptr, idle);
+      nuts_run<M, G, LDSL>(mc, L, st, 1, exmc_exp(da.log_epsilon), cap, wsink, (NoPipeWalk*)nullptr, idle);
       w_divergences += diverged ? 1 : 0;
       da.update(accept);
       if (in_window) {
@@ -2957,7 +3231,7 @@ __global__ void __launch_bounds__(kNutsBlock, M::kNutsWavesPerSimd) indep_kernel
     lf_total += (unsigned long long)t_n;
     div_total += t_div ? 1u : 0u;
   };
-  nuts_run<M, G, LDSL>(mc, L, st, P.num_samples, eps_final, P.max_depth, sink);
+  nuts_run<M, G, LDSL>(mc, L, st, P.num_samples, eps_final, P.max_depth, sink, (NoPipeWalk*)nullptr);
   chain_store<M, G>(P.st, C, chain, l, st);
   if (l == 0 && P.counters) {
     atomicAdd(&P.counters[0], lf_total);
