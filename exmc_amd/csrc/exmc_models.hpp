@@ -102,6 +102,10 @@ struct ModelDefaults {
   // doublings in six lane-batched evaluations (exmc_nuts.hpp tree_prefix); same bits. Needs
   // kLeafPairs and 11 lanes a group.
   static constexpr bool kTreePrefix = false;
+  // With kTreePrefix at 16 lanes a group: one walk of the chain's generator per transition, its words
+  // kept one per lane of the group's DPP row (exmc_nuts.hpp RngRowWindow). tree_prefix takes its ten
+  // uniforms from it and the next transition's momentum its normals; same words, same bits.
+  static constexpr bool kRngWindow = false;
 };
 
 // the dynamic LDS of the running kernel (every extern __shared__ array names the same base)
@@ -151,6 +155,8 @@ struct EightSchools : ModelDefaults {
   static constexpr bool kOuterLogPair = (G == 16);
   // doublings 0-2 of every tree as one straight-line unit ("Round 9")
   static constexpr bool kTreePrefix = (G == 16);
+  // ... and one generator walk per transition ("Round 10")
+  static constexpr bool kRngWindow = (G == 16);
   using MM = Math<kVregMath>;
   using Consts = EightSchoolsConsts;
   struct Lane {
@@ -1712,6 +1718,7 @@ struct RowDenseModel : M {
   // the outer merge's log pair is measured, and switched on, for the diagonal-mass kernel only
   static constexpr bool kOuterLogPair = false;
   static constexpr bool kTreePrefix = false;   // likewise (exmc_nuts.hpp tree_prefix)
+  static constexpr bool kRngWindow = false;    // (the window is built inside tree_prefix)
   static_assert(M::DPL == 1 && M::D <= 12, "row layout: one dimension per lane, D <= 12");
 };
 

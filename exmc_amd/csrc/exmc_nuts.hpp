@@ -595,16 +595,16 @@ __device__ __forceinline__ void draw_momentum_orbit(const NutsLane<M, G>& L, Rng
 // orbit form above) and is fetched from the lane of dimension i - 1 -- or, for the first draw of a
 // pass, taken from the state the pass started at -- only when draw i goes the long way. The first
 // pass starts at draw 0 in every group, so its steps need no `act` selects.
+// draw_momentum_lean_from: the same entered mid-way -- z holds the variates of draws [0, pos), rng stands
+// in front of draw pos (per group; D for a group that has nothing left to draw), `first` says that
+// every group of the wavefront is at draw 0.
 template <class M, int G>
-__device__ __forceinline__ void draw_momentum_lean(const NutsLane<M, G>& L, Rng& rng,
-                                                   double (&z)[M::DPL]) {
+__device__ __forceinline__ void draw_momentum_lean_from(const NutsLane<M, G>& L, Rng& rng,
+                                                        double (&z)[M::DPL], int pos, bool first) {
   constexpr int D = M::D, DPL = M::DPL;
   static_assert(G < 64, "the 64-lane layouts have the orbit form");
   const int base = (threadIdx.x & 63) & ~(G - 1);
-#pragma unroll
-  for (int k = 0; k < DPL; k++) z[k] = 0.0;
-  int pos = 0;   // draws [0, pos) are final and rng stands in front of draw pos
-  bool first = true;   // wave-uniform
+  // pos: draws [0, pos) are final and rng stands in front of draw pos; first: wave-uniform
   for (;;) {
     Rng r2 = rng;
     uint64_t sb[DPL];
@@ -675,6 +675,140 @@ __device__ __forceinline__ void draw_momentum_lean(const NutsLane<M, G>& L, Rng&
       rng = r2;
       pos = D;
     }
+  }
+}
+
+template <class M, int G>
+__device__ __forceinline__ void draw_momentum_lean(const NutsLane<M, G>& L, Rng& rng,
+                                                   double (&z)[M::DPL]) {
+#pragma unroll
+  for (int k = 0; k < M::DPL; k++) z[k] = 0.0;
+  draw_momentum_lean_from<M, G>(L, rng, z, 0, true);
+}
+
+// The per-row form of the orbit (M::kRngWindow; 16 lanes a group, a group = one DPP row): W steps from
+// the state S behind a transition's momentum, walked once by every lane, the tail word b_i of the
+// state i steps behind S kept on lane kOff + i of the row. State i is (b_{i-1}, b_i), so the window
+// holds states 1 .. W - 1. Its readers: the ten uniforms of tree_prefix (words 0..9, state 10 behind
+// them), the state behind the end-of-transition uniform (state 1), and the D normals of the NEXT
+// momentum, draw r reading word 1 + r + shift (draw_momentum_window).
+// Capture is a shift register, not a lane predicate per step (see draw_momentum_variates on what
+// unrolled rank == i compares cost): row_shl:1 moves every word one lane down and the row's last
+// lane, which has no source, keeps `old` = the fresh word.
+#ifndef EXMC_RNG_WINDOW
+// words: 12 + the largest shift the next momentum reads without stepping again. 14 by the instruction
+// count of the benchmark's launch (13 to 16 measured; DESIGN.md section 5, "Round 10")
+#define EXMC_RNG_WINDOW 14
+#endif
+// timing-only: 1 = the tree's uniforms alone (an 11-word window), 0 = off; DESIGN.md section 5, "Round 10"
+#ifndef EXMC_RNG_WINDOW_STAGE
+#define EXMC_RNG_WINDOW_STAGE 2
+#endif
+template <int W>
+struct RngRowWindow {
+  static_assert(W >= 11 && W <= 16, "ten uniforms and the state behind them; one DPP row");
+  static constexpr int kOff = 16 - W;
+  uint32_t lo, hi;
+  __device__ __forceinline__ void build(Rng r) {
+    lo = hi = 0;
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+      lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)r.b, (int)lo, 0x101, 0xF, 0xF, false);
+      hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(r.b >> 32), (int)hi, 0x101, 0xF, 0xF, false);
+      rng_advance(r);
+    }
+  }
+  // the word this lane holds: b_{lane - kOff}
+  __device__ __forceinline__ uint64_t own() const { return ((uint64_t)hi << 32) | (uint64_t)lo; }
+  // b_I on every lane of the row
+  template <int I>
+  __device__ __forceinline__ uint64_t word() const {
+    static_assert(I >= 0 && I < W, "word outside the window");
+    const uint32_t l = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, 0x150 + kOff + I, 0xF, 0xF, true);   // row_newbcast
+    const uint32_t h = (uint32_t)__builtin_amdgcn_mov_dpp((int)hi, 0x150 + kOff + I, 0xF, 0xF, true);
+    return ((uint64_t)h << 32) | (uint64_t)l;
+  }
+  template <int I>
+  __device__ __forceinline__ Rng state() const { return Rng{word<I - 1>(), word<I>()}; }
+  // lane l of the row: b_{l + 1}, the word of draw l at shift 0 (0 where that lies past the row)
+  __device__ __forceinline__ uint64_t next_rank() const {
+    const uint32_t l = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, 0x100 + kOff + 1, 0xF, 0xF, true);   // row_shl
+    const uint32_t h = (uint32_t)__builtin_amdgcn_mov_dpp((int)hi, 0x100 + kOff + 1, 0xF, 0xF, true);
+    return ((uint64_t)h << 32) | (uint64_t)l;
+  }
+  // b_p for a per-lane position p in [0, W)
+  __device__ __forceinline__ uint64_t at(int p) const {
+    const int src = (((threadIdx.x & 63) & ~15) | (kOff + p)) << 2;
+    const uint32_t l = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)lo);
+    const uint32_t h = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)hi);
+    return ((uint64_t)h << 32) | (uint64_t)l;
+  }
+};
+
+// The D normals of a momentum from the window the previous transition's tree_prefix built (identity
+// order, one dimension a lane). The window's state 1 is where this momentum starts, so draw r reads
+// word 1 + r + shift, shift = the words earlier draws of this momentum consumed beyond their first
+// (per group); every lane tests its own word at once, as in draw_momentum_lean, and a draw whose
+// word normal_fast rejects is made the long way from the state read out of the window, after which
+// only shift changes (draw_momentum_orbit). While every group is at shift 0 -- always in the first
+// round -- a lane's word comes by one DPP shift. The state behind the momentum is 1 + D + shift; a
+// group whose shift has grown past kMaxShift leaves with the state the long-way draw left and
+// `left` = the draw it stands in front of, for the stepping loop (draw_momentum_lean_from); D for
+// a group that is done.
+template <class M, int G, int W>
+__device__ __forceinline__ void draw_momentum_window(const NutsLane<M, G>& L, const RngRowWindow<W>& win,
+                                                     Rng& rng, double (&z)[M::DPL], int& left) {
+  constexpr int D = M::D;
+  static_assert(G == 16 && M::DPL == 1, "a group is one DPP row with one dimension a lane");
+  static_assert(W >= D + 2, "the state behind the momentum at shift 0");
+  constexpr int kMaxShift = W - D - 2;
+  const int base = (threadIdx.x & 63) & ~(G - 1);
+  const int rank = L.rank[0];
+  z[0] = 0.0;
+  int pos = 0, shift = 0;   // draws [0, pos) are final
+  left = D;
+  uint64_t la = 0, lb = 0;  // the state a group left the window with
+  bool flat = true;         // wave-uniform: every group is at shift 0
+  for (;;) {
+    const bool live = L.valid[0] && (rank >= pos);
+    const uint64_t w = flat ? win.next_rank() : win.at(live ? 1 + rank + shift : 0);
+    double zz;
+    const bool acc = normal_fast(rng_scramble(w), L.zt, zz);
+    const bool fail = live && !acc;
+    z[0] = (live && acc) ? zz : z[0];
+    const unsigned long long m = __ballot(fail ? 1 : 0);
+    const unsigned long long gm = (m >> base) & ((1ULL << G) - 1ULL);
+    const int j = (gm != 0) ? (__ffsll((long long)gm) - 1) : D;   // first draw that needs the long way
+    if (m == 0) break;
+    flat = false;
+    if (j < D) {
+      const int pj = 1 + j + shift;   // <= D + kMaxShift < W
+      Rng rj;
+      rj.a = win.at(pj - 1);
+      rj.b = win.at(pj);
+      int words = 0;
+      zz = rng_normal_counted(rj, L.zt, L.nor_r, words);
+      z[0] = (rank == j) ? zz : z[0];
+      shift += words - 1;
+      pos = j + 1;
+      if (shift > kMaxShift) {
+        la = rj.a;
+        lb = rj.b;
+        left = pos;
+        pos = D;
+      }
+    } else {
+      pos = D;
+    }
+  }
+  if (flat) {
+    rng = win.template state<D + 1>();
+  } else {
+    const bool gone = shift > kMaxShift;
+    const int pe = gone ? 1 : D + 1 + shift;
+    const uint64_t ea = win.at(pe - 1), eb = win.at(pe);
+    rng.a = gone ? la : ea;
+    rng.b = gone ? lb : eb;
   }
 }
 
@@ -1275,19 +1409,47 @@ struct TreeTop {
 // integrating its own trajectory as scratch. On return T is what the walk's doubling loop holds
 // before depth 3 and trng stands behind the ten uniforms (a group that stopped drew fewer; its copy
 // is discarded). (q, p, g): left at the last leaf, the scratch state an idle group goes on with.
-template <class M, int G>
+//
+// Win = RngRowWindow<W> (M::kRngWindow): the ten uniforms are not drawn one after the other on every
+// lane. One walk of W steps from trng fills the group's window, lane kOff + i scrambles and converts
+// word i, and u[i] lives on that lane alone: a uniform is broadcast where it is consumed -- the
+// directions before the leapfrogs, the merges' after them -- and batch 2 evaluates each candidate's
+// log_unit on the lane that holds it (the four log_ge1 arguments go to the lanes of the three
+// directions and of word 10), with each lane's own fix-up applied before the broadcast.
+struct NoRngWindow {
+  static constexpr int kOff = 0;
+};
+template <int I>
+using IntC = std::integral_constant<int, I>;
+
+template <class M, int G, class Win = NoRngWindow>
 __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const NutsLane<M, G>& L,
                                             double eps, double jlp0, int max_depth, Rng& trng,
                                             TreeTop<M::DPL> T, double (&q)[M::DPL], double (&p)[M::DPL],
-                                            double (&g)[M::DPL]) {
+                                            double (&g)[M::DPL], Win* win = nullptr) {
   constexpr int DPL = M::DPL;
   using MM = Math<M::kVregMath>;
   static_assert(G >= 11, "one lane per argument of the widest batch");
   static_assert(!M::kRegradProposal, "the proposal's gradient travels with it");
+  constexpr bool kWin = !std::is_same<Win, NoRngWindow>::value;
   double u[10];
+  double ul = 0.0;   // kWin: u[i] on lane kOff + i of the group
+  if constexpr (kWin) {
+    static_assert(G == 16, "a group is one DPP row");
+    win->build(trng);
+    ul = (double)(rng_scramble(win->own()) >> 5) * 0x1p-53;
+    trng = win->template state<10>();
+  } else {
 #pragma unroll
-  for (int i = 0; i < 10; i++) u[i] = rng_uniform(trng);
-  const bool r0 = u[0] > 0.5, r1 = u[2] > 0.5, r2 = u[5] > 0.5;   // tree.ex:403
+    for (int i = 0; i < 10; i++) u[i] = rng_uniform(trng);
+  }
+  // u[I], for a compile-time I
+  auto U = [&](auto ic) -> double {
+    constexpr int I = decltype(ic)::value;
+    if constexpr (kWin) return group_bcast_c<G, Win::kOff + I>(ul);
+    else return u[I];
+  };
+  const bool r0 = U(IntC<0>{}) > 0.5, r1 = U(IntC<2>{}) > 0.5, r2 = U(IntC<5>{}) > 0.5;   // tree.ex:403
 
   // ---- the seven leapfrogs (batched_leapfrog.ex:79-85), as leaf_pair integrates them ----
   PipeLeaf<DPL> f0, f1, f2, f3, f4, f5, f6;
@@ -1350,8 +1512,31 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   accept(f4, x[4]); accept(f5, x[5]); accept(f6, x[6]);
 
   // ---- batch 2 ----
-  double y[11] = {1.0 + x[7], 1.0 + x[8], 1.0 + x[9], 1.0 + x[10], u[1], u[3], u[4], u[6], u[7], u[8], u[9]};
-  {
+  double y[11] = {1.0 + x[7], 1.0 + x[8], 1.0 + x[9], 1.0 + x[10], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (kWin) {
+    constexpr int o = Win::kOff;
+    const int l = L.l;
+    const bool ge1 = (l == o) || (l == o + 2) || (l == o + 5) || (l == o + 10);
+    double a = ul;
+    a = (l == o) ? y[0] : a;
+    a = (l == o + 2) ? y[1] : a;
+    a = (l == o + 5) ? y[2] : a;
+    a = (l == o + 10) ? y[3] : a;
+    const double r = MM::log_main(a);
+    const double v = ge1 ? exmc_log_ge1_fix(a, r) : exmc_log_unit_fix(a, r);
+    y[0] = group_bcast_c<G, o>(v);
+    y[1] = group_bcast_c<G, o + 2>(v);
+    y[2] = group_bcast_c<G, o + 5>(v);
+    y[3] = group_bcast_c<G, o + 10>(v);
+    y[4] = group_bcast_c<G, o + 1>(v);
+    y[5] = group_bcast_c<G, o + 3>(v);
+    y[6] = group_bcast_c<G, o + 4>(v);
+    y[7] = group_bcast_c<G, o + 6>(v);
+    y[8] = group_bcast_c<G, o + 7>(v);
+    y[9] = group_bcast_c<G, o + 8>(v);
+    y[10] = group_bcast_c<G, o + 9>(v);
+  } else {
+    y[4] = u[1]; y[5] = u[3]; y[6] = u[4]; y[7] = u[6]; y[8] = u[7]; y[9] = u[8]; y[10] = u[9];
     double v[11];
 #pragma unroll
     for (int i = 0; i < 11; i++) v[i] = y[i];
@@ -1426,11 +1611,11 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   lane_batch<G>(w, L.l, [](double v) { return MM::exp_le0(v); });
   PipeUnit<DPL> c1, ca, cb;
   pipe_pair_unit<M, G>(L, f1, f2, true, q1, g1, trng, c1, [&](auto, double, double) { return lsw12; },
-                       [&](auto, double, double) { return w[0]; }, [&](Rng&) { return u[3]; });
+                       [&](auto, double, double) { return w[0]; }, [&](Rng&) { return U(IntC<3>{}); });
   pipe_pair_unit<M, G>(L, f3, f4, true, q2, g2, trng, ca, [&](auto, double, double) { return lsw34; },
-                       [&](auto, double, double) { return w[1]; }, [&](Rng&) { return u[6]; });
+                       [&](auto, double, double) { return w[1]; }, [&](Rng&) { return U(IntC<6>{}); });
   pipe_pair_unit<M, G>(L, f5, f6, true, f4.q, f4.g, trng, cb, [&](auto, double, double) { return lsw56; },
-                       [&](auto, double, double) { return w[2]; }, [&](Rng&) { return u[7]; });
+                       [&](auto, double, double) { return w[2]; }, [&](Rng&) { return U(IntC<7>{}); });
   // doubling 2's first pair parks and waits for the second unless it diverged or turned
   const bool parked = !(ca.div || ca.turn);
 
@@ -1449,7 +1634,7 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   double e[2] = {c56 - lsw_m, MM::lse_arg(T.lsw, parked ? lsw_m : c34)};
   lane_batch<G>(e, L.l, [](double v) { return MM::exp_le0(v); });
   if (parked) {
-    const double um = f5.div ? u[7] : u[8];
+    const double um = f5.div ? U(IntC<7>{}) : U(IntC<8>{});
     const bool use_b = um < e[0];
     if (!use_b) {
       cb.logpP = ca.logpP;
@@ -1543,6 +1728,16 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
   double eps_dir = eps;
   Rng trng = st.rng;
   const bool has = L.alive;   // false: a lane group kept only for wave-cooperative models
+  // M::kTreePrefix: doublings 0-2 straight-line (tree_prefix), the walk below from depth 3 on
+  constexpr bool kPrefix = M::kTreePrefix && M::kLeafPairs && Pipe::kTreePrefix && EXMC_ABLATE == 0;
+  // M::kRngWindow: the generator is walked once per transition, inside tree_prefix; the window it
+  // leaves holds the state behind the end-of-transition uniform and the words of the next momentum,
+  // so from the second transition of a call on the momentum steps no generator (the first has no
+  // window and takes the stepping loop). st.rng is the true state at every transition boundary.
+  constexpr bool kWindow = kPrefix && M::kRngWindow && G == 16 && EXMC_RNG_WINDOW_STAGE >= 1;
+  constexpr bool kWinMomentum = kWindow && EXMC_RNG_WINDOW_STAGE >= 2 && DPL == 1 && M::kLeanMomentum && !M::kRowDense;
+  using Win = RngRowWindow<kWinMomentum ? EXMC_RNG_WINDOW : 11>;
+  Win win{0, 0};
 
   EXMC_PROF_DECL
   for (int draw = 0; draw < n_draws; draw++) {
@@ -1563,8 +1758,21 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
       }
     }
     if (has) {
-      if (have_z) momentum_from_variates<M, G>(L, z_pre, pL);
-      else draw_momentum<M, G>(L, st.rng, pL);
+      if (have_z) {
+        momentum_from_variates<M, G>(L, z_pre, pL);
+      } else if (kWinMomentum && L.perm == nullptr) {
+        if constexpr (kWinMomentum) {
+          // one stepping loop for both of its uses: a call's first momentum (no window yet) and the
+          // groups that ran past the window
+          int left = 0;
+          if (draw > 0) draw_momentum_window<M, G>(L, win, st.rng, z_pre, left);
+          if (draw == 0 || __any((left < M::D) ? 1 : 0) != 0)
+            draw_momentum_lean_from<M, G>(L, st.rng, z_pre, left, draw == 0);
+          momentum_from_variates<M, G>(L, z_pre, pL);
+        }
+      } else {
+        draw_momentum<M, G>(L, st.rng, pL);
+      }
       jlp0 = st.logp - mass_ke<M, G>(L, pL);
       trng = st.rng;  // the tree consumes a copy (sampler.ex:897 discards its draws)
 #pragma unroll
@@ -1587,9 +1795,13 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
     idle();
     EXMC_PROF(0)
 
-    // M::kTreePrefix: doublings 0-2 straight-line (tree_prefix), the walk below from depth 3 on
-    constexpr bool kPrefix = M::kTreePrefix && M::kLeafPairs && Pipe::kTreePrefix && EXMC_ABLATE == 0;
-    if constexpr (kPrefix) {
+    if constexpr (kWindow) {
+      tree_prefix<M, G, Win>(mc, L, eps, jlp0, max_depth, trng,
+                             TreeTop<DPL>{qL, pL, gL, qR, pR, gR, t_rho, t_qp, t_gp, t_logpP, t_lsw, t_acc,
+                                          t_n, t_depth, t_div, t_turn, alive},
+                             q, p, g, &win);
+      EXMC_PROF(7)
+    } else if constexpr (kPrefix) {
       tree_prefix<M, G>(mc, L, eps, jlp0, max_depth, trng,
                         TreeTop<DPL>{qL, pL, gL, qR, pR, gR, t_rho, t_qp, t_gp, t_logpP, t_lsw, t_acc,
                                      t_n, t_depth, t_div, t_turn, alive},
@@ -1949,7 +2161,8 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
       (void)M::logp_grad(mc, L.ln, l, t_qp, t_gp);
     }
     if (has) {
-      (void)rng_uniform(st.rng);
+      if constexpr (kWindow) st.rng = win.template state<1>();   // the window was walked from this state
+      else (void)rng_uniform(st.rng);
       st.logp = t_logpP;
 #pragma unroll
       for (int k = 0; k < DPL; k++) { st.q[k] = t_qp[k]; st.g[k] = t_gp[k]; }
