@@ -423,6 +423,33 @@ __device__ __forceinline__ void row_seqsum(double& a0, double& a1, double& a2, d
   EXMC_SEQSUM_ASM(EXMC_SEQ3, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
                   [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [v2] "v"(v2) EXMC_COMMA [one] "v"(one))
 }
+// The lane-range form: a_j <- a_j + v_j[lane I0] + ... + v_j[lane I0 + NL - 1], the same chain in one
+// asm block, for a caller whose lanes below I0 hold no term (EightSchools' likelihood sums: lanes 0
+// and 1 are mu and log tau). From a_j = +0.0 the result has the bits of the full chain over terms
+// that are +0.0 below I0 -- fma(+0.0, 1, +0.0) = +0.0 -- and what lanes outside the range hold is
+// never read. The first fmac stays an fmac: fma(-0.0, 1, +0.0) is +0.0, a move would keep -0.0.
+#define EXMC_FMAC_R(A, V, I) \
+  "v_fmac_f64_dpp %[" #A "], %[" #V "], %[one] row_newbcast:%[l" #I "] row_mask:0xf bank_mask:0xf\n\t"
+#define EXMC_SEQ3R(I) EXMC_FMAC_R(a0, v0, I) EXMC_FMAC_R(a1, v1, I) EXMC_FMAC_R(a2, v2, I)
+#define EXMC_LANE_R(I) [l##I] "n"((I0 + I) & 15)
+template <int I0, int NL>
+__device__ __forceinline__ void row_seqsum_lanes(double& a0, double& a1, double& a2, double v0, double v1,
+                                                 double v2) {
+  static_assert(I0 >= 0 && NL >= 1 && NL <= 12 && I0 + NL <= 16, "a lane range of one DPP row");
+  const double one = seq_one();
+  EXMC_SEQSUM_ASM(EXMC_SEQ3R, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
+                  [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [v2] "v"(v2) EXMC_COMMA [one] "v"(one) EXMC_COMMA
+                  EXMC_LANE_R(0) EXMC_COMMA EXMC_LANE_R(1) EXMC_COMMA EXMC_LANE_R(2) EXMC_COMMA EXMC_LANE_R(3) EXMC_COMMA
+                  EXMC_LANE_R(4) EXMC_COMMA EXMC_LANE_R(5) EXMC_COMMA EXMC_LANE_R(6) EXMC_COMMA EXMC_LANE_R(7) EXMC_COMMA
+                  EXMC_LANE_R(8) EXMC_COMMA EXMC_LANE_R(9) EXMC_COMMA EXMC_LANE_R(10) EXMC_COMMA EXMC_LANE_R(11))
+}
+// Timing only ("Round 11"): the three pieces of that round, each of which
+// builds alone for its counter run. 1: EightSchools' likelihood sums over lanes 2..9
+// (exmc_models.hpp eval_row_grad); 2: one U-turn test in the outer merge of doubling 0
+// (exmc_nuts.hpp tree_prefix); 4: eval_row_grad's two range watches as one. Same bits with any set.
+#ifndef EXMC_ROW_SUM_PIECES
+#define EXMC_ROW_SUM_PIECES 7
+#endif
 // ---- a dense D x D matrix against a vector held one entry per lane (row layout of a 16-lane
 // chain group): lane i keeps row i of the matrix in registers and
 //     acc = fma(x[lane j], c[j], acc)   for j = 0 .. NL-1, from 0.0

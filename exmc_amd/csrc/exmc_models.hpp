@@ -222,18 +222,25 @@ struct EightSchools : ModelDefaults {
     const double th = q[0];
     const double theta = mu + tau * th;
     const double resid = ln.y[0] - theta;
-    dv.watch_if(isth, resid);
+    constexpr bool kThetaLanes = (EXMC_ROW_SUM_PIECES & 1) != 0, kOneWatch = (EXMC_ROW_SUM_PIECES & 4) != 0;
+    if constexpr (!kOneWatch) dv.watch_if(isth, resid);
     dv.watch_if(isth, ln.sg[0].b);
     const double z = dv(resid, ln.sg[0]);
     const double a = dv(z, ln.sg[0]);
-    const double Lk = isth ? ((-0.5 * (z * z)) - ln.lsg[0]) : 0.0;
-    const double Ak = isth ? a : 0.0;
-    const double Bk = isth ? (a * th) : 0.0;
+    const double Lk = (-0.5 * (z * z)) - ln.lsg[0];
+    const double Ak = a;
+    const double Bk = a * th;
     double lik = 0.0, sa = 0.0, sb = 0.0;
-    row_seqsum<D>(lik, sa, sb, Lk, Ak, Bk);
+    // the three likelihood sums over the lanes that hold a term, 2 .. 9: the other lanes' values are
+    // not read, so they need no select (the full chain added +0.0 for lanes 0 and 1: the same bits)
+    if constexpr (kThetaLanes) row_seqsum_lanes<2, D - 2>(lik, sa, sb, Lk, Ak, Bk);
+    else row_seqsum<D>(lik, sa, sb, isth ? Lk : 0.0, isth ? Ak : 0.0, isth ? Bk : 0.0);
     // hyper-parameter lanes
     const double x = l0 ? (mu - 0.0) : tau;
-    dv.watch_if(l0, x);                      // tau = exp(clamp200(.)) is in range by construction
+    // one range watch for the disjoint lanes of the two watched numerators: the residual on a theta
+    // lane, mu on lane 0 (tau = exp(clamp200(.)) is in range by construction)
+    if constexpr (kOneWatch) dv.watch_if(isth || l0, l0 ? x : resid);
+    else dv.watch_if(l0, x);
     const double zh = dv(x, ln.five);        // zmu | zt
     const double zh2 = zh * zh;
     const double w = dv(zh, ln.five);        // zmu / 5 | zt / 5

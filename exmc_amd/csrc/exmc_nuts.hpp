@@ -1555,7 +1555,12 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   const double c56 = f5.div ? f5.lsw : lsw56;
 
   // merge_trajectories (tree.ex:1479-1568) of subtree c, as nuts_run's outer merge performs it
-  auto outer = [&](const PipeUnit<DPL>& c, bool go_right, double log1pe, double logu, int depth) {
+  // dc: the doubling, an IntC. In doubling 0 the trajectory is the start point alone and c one leaf:
+  // T.rho = T.pL = T.pR and c.rho = c.pin = c.p, so the three U-turn tests of the merge have the same
+  // operands (rho, start, leaf) and one decides all three
+  auto outer = [&](const PipeUnit<DPL>& c, bool go_right, double log1pe, double logu, auto dc) {
+    constexpr int depth = decltype(dc)::value;
+    constexpr bool kOneTest = depth == 0 && (EXMC_ROW_SUM_PIECES & 2) != 0;
     if (!T.alive) return;
     const double lsw = MM::lse_finish(T.lsw, c.lsw, log1pe);
     const bool use_sub = logu < (c.lsw - T.lsw);
@@ -1570,17 +1575,25 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
 #pragma unroll
     for (int k = 0; k < DPL; k++) rho[k] = T.rho[k] + c.rho[k];
     if (!turning) {
-      double nearp[DPL], farp[DPL], s2[DPL], s3[DPL];
+      double nearp[DPL], farp[DPL];
 #pragma unroll
       for (int k = 0; k < DPL; k++) {
         nearp[k] = go_right ? T.pR[k] : T.pL[k];
         farp[k] = go_right ? T.pL[k] : T.pR[k];
-        s2[k] = T.rho[k] + c.pin[k];
-        s3[k] = nearp[k] + c.rho[k];
       }
-      bool c1, c23;
-      mass_uturn3<M, G>(L, rho, farp, c.p, s2, farp, c.pin, s3, nearp, c.p, c1, c23);
-      turning = c1 || c23;
+      if constexpr (kOneTest) {
+        turning = mass_uturn<M, G>(L, rho, farp, c.p);
+      } else {
+        double s2[DPL], s3[DPL];
+#pragma unroll
+        for (int k = 0; k < DPL; k++) {
+          s2[k] = T.rho[k] + c.pin[k];
+          s3[k] = nearp[k] + c.rho[k];
+        }
+        bool c1, c23;
+        mass_uturn3<M, G>(L, rho, farp, c.p, s2, farp, c.pin, s3, nearp, c.p, c1, c23);
+        turning = c1 || c23;
+      }
     }
 #pragma unroll
     for (int k = 0; k < DPL; k++) {
@@ -1604,7 +1617,7 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   for (int k = 0; k < DPL; k++) { s0q[k] = T.qL[k]; s0g[k] = T.gL[k]; }
   PipeUnit<DPL> c;
   pipe_pair_unit<M, G>(L, f0, f0, false, s0q, s0g, trng, c);
-  outer(c, r0, y[3], y[4], 0);
+  outer(c, r0, y[3], y[4], IntC<0>{});
 
   // ---- batch 3 (T.lsw: the trajectory's after doubling 0) and the pair units ----
   double w[5] = {f2.lsw - lsw12, f4.lsw - lsw34, f6.lsw - lsw56, MM::lse_arg(lsw34, c56), MM::lse_arg(T.lsw, c12)};
@@ -1628,7 +1641,7 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
     z[1] = exmc_log_ge1_fix(v1, z[1]);
   }
   const double lsw_m = MM::lse_finish(lsw34, c56, z[0]);
-  outer(c1, r1, z[1], f1.div ? y[5] : y[6], 1);
+  outer(c1, r1, z[1], f1.div ? y[5] : y[6], IntC<1>{});
 
   // ---- batch 5; the level-1 merge of doubling 2 (tree.ex:1390-1476), as nuts_run's ascent ----
   double e[2] = {c56 - lsw_m, MM::lse_arg(T.lsw, parked ? lsw_m : c34)};
@@ -1666,7 +1679,7 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
 
   // ---- batch 6, doubling 2's outer merge ----
   const double lu2 = f3.div ? y[7] : (!parked ? y[8] : (f5.div ? y[9] : y[10]));
-  outer(cb, r2, MM::log_ge1(1.0 + e[1]), lu2, 2);
+  outer(cb, r2, MM::log_ge1(1.0 + e[1]), lu2, IntC<2>{});
 }
 
 // n_draws NUTS transitions of this group's chain. sink(draw, q, logp, depth, n_steps, divergent,
