@@ -1365,10 +1365,14 @@ static double run_warmup(const exo_model* m, cstate* s, double eps, double* im, 
   return exo_da_finalize(&da);
 }
 
-static void run_sampling(const exo_model* m, cstate* s, double eps, const double* im, exo_opts o,
-                         exo_trace tr, size_t base, long* leapfrogs, exo_cfg c) {
+/* rng_states (NULL: none kept): the generator before each transition and after the last,
+ * [num_samples + 1][2] as (a, b) */
+static void run_sampling_states(const exo_model* m, cstate* s, double eps, const double* im, exo_opts o,
+                                exo_trace tr, size_t base, long* leapfrogs, uint64_t* rng_states,
+                                exo_cfg c) {
   /* sampler.ex:929-973 */
   int d = m->d;
+  if (rng_states) { rng_states[0] = s->rng.a; rng_states[1] = s->rng.b; }
   for (int i = 0; i < o.num_samples; i++) {
     step_info info;
     nuts_step(m, s, eps, im, o.max_tree_depth, &info, c);
@@ -1381,7 +1385,13 @@ static void run_sampling(const exo_model* m, cstate* s, double eps, const double
     if (tr.accept_prob) tr.accept_prob[k] = info.accept;
     if (tr.energy) tr.energy[k] = info.energy;
     if (leapfrogs) *leapfrogs += info.n_steps;
+    if (rng_states) { rng_states[2 * (i + 1)] = s->rng.a; rng_states[2 * (i + 1) + 1] = s->rng.b; }
   }
+}
+
+static void run_sampling(const exo_model* m, cstate* s, double eps, const double* im, exo_opts o,
+                         exo_trace tr, size_t base, long* leapfrogs, exo_cfg c) {
+  run_sampling_states(m, s, eps, im, o, tr, base, leapfrogs, NULL, c);
 }
 
 static double warmup_chain0(const exo_model* m, const double* init_q, exo_opts o, cstate* s,
@@ -1408,6 +1418,17 @@ int exo_sample(const exo_model* m, const double* init_q, exo_opts o, exo_trace t
   st->step_size = warmup_chain0(m, init_q, o, &s, st->inv_mass, c);
   st->total_leapfrogs = 0;
   run_sampling(m, &s, st->step_size, st->inv_mass, o, tr, 0, &st->total_leapfrogs, c);
+  st->divergences = s.divergences;
+  return 0;
+}
+
+int exo_sample_rng_states(const exo_model* m, const double* init_q, exo_opts o, exo_trace tr,
+                          exo_stats* st, uint64_t* rng_states, exo_cfg c) {
+  /* exo_sample, and the chain's generator around every sampling transition */
+  cstate s;
+  st->step_size = warmup_chain0(m, init_q, o, &s, st->inv_mass, c);
+  st->total_leapfrogs = 0;
+  run_sampling_states(m, &s, st->step_size, st->inv_mass, o, tr, 0, &st->total_leapfrogs, rng_states, c);
   st->divergences = s.divergences;
   return 0;
 }

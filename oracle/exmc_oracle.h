@@ -176,6 +176,11 @@ typedef struct {
 /* init_q NULL => 0.1*normal_s per dim (sampler.ex:339-349) */
 int exo_sample(const exo_model* m, const double* init_q, exo_opts o, exo_trace tr, exo_stats* st,
                exo_cfg cfg);
+/* exo_sample, and the chain's generator state (a, b) before each of the num_samples sampling
+ * transitions and after the last: rng_states [num_samples + 1][2]. Per transition the main stream
+ * takes d normals (the momentum) and one uniform (sampler.ex:854-925); the tree draws from a copy. */
+int exo_sample_rng_states(const exo_model* m, const double* init_q, exo_opts o, exo_trace tr,
+                          exo_stats* st, uint64_t* rng_states, exo_cfg cfg);
 /* shared warmup on chain 0 (plain path), then chains seeded seed+7919*i (sampler.ex:1053-1130).
  * Traces are chain-major: draws [n_chains][num_samples][d] etc. chain_lo..chain_hi selects a
  * sub-range of chains to run (for sharding); n_threads > 1 runs chains on host threads. */

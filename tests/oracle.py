@@ -147,6 +147,8 @@ def lib():
     L.exo_build_windows.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, C.c_int]
     L.exo_build_windows.restype = C.c_int
     L.exo_sample.argtypes = [C.c_void_p, dp, Opts, Trace, C.POINTER(Stats), Cfg]
+    L.exo_sample_rng_states.argtypes = [C.c_void_p, dp, Opts, Trace, C.POINTER(Stats),
+                                        C.POINTER(C.c_uint64), Cfg]
     L.exo_sample_chains.argtypes = [C.c_void_p, dp, C.c_int, C.c_int, C.c_int, Opts, Trace,
                                     C.POINTER(Stats), C.c_int, Cfg]
     L.exo_warmup.argtypes = [C.c_void_p, dp, Opts, C.POINTER(Stats), Cfg]
@@ -286,6 +288,20 @@ def sample(model, init_q=None, num_warmup=1000, num_samples=1000, max_tree_depth
     lib().exo_sample(model.h, iq, Opts(num_warmup, num_samples, max_tree_depth, target_accept, seed),
                      tr, C.byref(st), cfg)
     return t, st
+
+
+def sample_rng_states(model, init_q=None, num_warmup=1000, num_samples=1000, max_tree_depth=10,
+                      target_accept=0.8, seed=0, cfg=None):
+    """sample, and the chain's generator (a, b) before each sampling transition and after the last:
+    (trace, stats, states [num_samples + 1][2] uint64)."""
+    cfg = cfg or Cfg(0, 1)
+    t, tr = alloc_trace(num_samples, model.d)
+    st = Stats()
+    states = np.zeros((num_samples + 1, 2), np.uint64)
+    iq = None if init_q is None else dptr(arr(init_q))
+    lib().exo_sample_rng_states(model.h, iq, Opts(num_warmup, num_samples, max_tree_depth, target_accept, seed),
+                                tr, C.byref(st), states.ctypes.data_as(C.POINTER(C.c_uint64)), cfg)
+    return t, st, states
 
 
 def warmup(model, init_q=None, num_warmup=1000, max_tree_depth=10, target_accept=0.8, seed=0,

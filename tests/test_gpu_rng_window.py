@@ -13,8 +13,9 @@ asserts that the stream shows what the case is there for. 33 chains: chains 4w .
 wave, and the last wave has one live lane group.
 
 The streaming twin of the kernel starts from a seed and its own warmup (exmc_hip_stream_begin), not
-from given states and generators, so these cases cannot be put through it; the existing streaming
-tests (tests/test_gpu_parity.py, tests/test_gpu_nif_shim.py) are its check.
+from given states and generators. Its windows, shifts, prefix divergences and depth caps are reached
+by steering that start (num_warmup, target_accept, max_tree_depth, seed) and held to the checker's
+sample/3 in tests/test_gpu_stream_push.py.
 """
 import ctypes as C
 from collections import Counter
