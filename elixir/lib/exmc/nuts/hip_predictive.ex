@@ -41,9 +41,11 @@ defmodule Exmc.NUTS.HipPredictive do
   end
 
   # the kinds of include/exmc_hip.h: 1 simple, 2 eight_schools, 3 sv, 4 logistic, 5 radon, 7 sv_ncp
-  defp datum_names(2, n), do: for(j <- 0..(n - 1), do: "y_obs_#{j}")
-  defp datum_names(1, n), do: for(i <- 0..(n - 1), do: {"y_obs", i})
-  defp datum_names(kind, n) when kind in [3, 7], do: for(t <- 0..(n - 1), do: {"returns", t})
-  defp datum_names(5, n), do: for(i <- 0..(n - 1), do: {"radon", i})
-  defp datum_names(_kind, n), do: for(i <- 0..(n - 1), do: {"y", i})
+  # (Exmc.NUTS.HipLooPit names its datums with it too)
+  @doc false
+  def datum_names(2, n), do: for(j <- 0..(n - 1), do: "y_obs_#{j}")
+  def datum_names(1, n), do: for(i <- 0..(n - 1), do: {"y_obs", i})
+  def datum_names(kind, n) when kind in [3, 7], do: for(t <- 0..(n - 1), do: {"returns", t})
+  def datum_names(5, n), do: for(i <- 0..(n - 1), do: {"radon", i})
+  def datum_names(_kind, n), do: for(i <- 0..(n - 1), do: {"y", i})
 end

@@ -55,6 +55,10 @@ PREDICTIVE_EXPORTS = ["exmc_hip_posterior_predictive", "exmc_hip_posterior_predi
 PPC_EXPORTS = ["exmc_hip_ppc", "exmc_hip_ppc_host"]
 PPC_BLOCK = 64
 
+# include/exmc_hip_loo_pit.h: PSIS-LOO-PIT, the replicates weighted with the smoothed LOO weights
+LOO_PIT_EXPORTS = ["exmc_hip_loo_pit", "exmc_hip_loo_pit_host", "exmc_hip_loo_pit_from_ll"]
+LOO_PIT_ROWS = ("p_lt", "p_eq", "pit", "k")
+
 # include/exmc_hip_convergence.h: rank-normalised R-hat and bulk / tail / mean ESS across chains
 CONVERGENCE_EXPORTS = ["exmc_hip_convergence", "exmc_hip_convergence_host"]
 CONVERGENCE_ROWS = ("rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean")
@@ -197,6 +201,9 @@ def bind(path):
     L.exmc_hip_posterior_predictive_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, up, dp]
     L.exmc_hip_ppc.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, dp, dp, dp]
     L.exmc_hip_ppc_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp]
+    L.exmc_hip_loo_pit.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
+    L.exmc_hip_loo_pit_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, C.c_size_t, dp]
+    L.exmc_hip_loo_pit_from_ll.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.exmc_hip_convergence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
     L.exmc_hip_convergence_host.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_size_t, dp]
     _libs[path] = L

@@ -13,6 +13,7 @@
 #include "../../include/exmc_hip_advi.h"
 #include "../../include/exmc_hip_predictive.h"
 #include "../../include/exmc_hip_ppc.h"
+#include "../../include/exmc_hip_loo_pit.h"
 #include "../../include/exmc_hip_convergence.h"
 
 #include <hip/hip_runtime.h>
@@ -2085,26 +2086,45 @@ struct PsisScratch {
   }
 };
 
-// the three launches over ll[S][Nb][C]; rows out[3][N], this block's datums from i0
-int psis_launch(hipStream_t stream, const PsisScratch& sc, const double* ll, int S, int Nb, int C, int N, int i0,
-                double* out) {
-  const long long n = (long long)S * C;
-  const IcGrid g = ic_grid(S, C, Nb);
-  if (sc.P <= kPsisLdsPairs) {
-    const size_t lds = psis_tail_lds_bytes(sc.P);
-    hipLaunchKernelGGL(psis_tail_kernel<true>, dim3((unsigned)Nb), dim3(kPsisBlock), lds, stream, ll, S, Nb, C, sc.M,
-                       sc.P, sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(), sc.meta.as<double>());
+// where psis_tail_kernel leaves the tails of the datums it is launched over: rows of P entries (keys, idx,
+// xs) and kPsisMeta doubles per datum, from these base pointers
+struct PsisTables {
+  uint64_t* keys;
+  uint32_t* idx;
+  double* xs;
+  double* meta;
+  int M, P;
+};
+PsisTables psis_tables(const PsisScratch& sc) {
+  return {sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(), sc.meta.as<double>(), sc.M, sc.P};
+}
+
+// the tails of ll[S][Nb][C] into the tables
+int psis_tails(hipStream_t stream, const PsisTables& t, const double* ll, int S, int Nb, int C) {
+  if (t.P <= kPsisLdsPairs) {
+    const size_t lds = psis_tail_lds_bytes(t.P);
+    hipLaunchKernelGGL(psis_tail_kernel<true>, dim3((unsigned)Nb), dim3(kPsisBlock), lds, stream, ll, S, Nb, C, t.M,
+                       t.P, t.keys, t.idx, t.xs, t.meta);
   } else {
-    hipLaunchKernelGGL(psis_tail_kernel<false>, dim3((unsigned)Nb), dim3(kPsisBlock), 0, stream, ll, S, Nb, C, sc.M,
-                       sc.P, sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(), sc.meta.as<double>());
+    hipLaunchKernelGGL(psis_tail_kernel<false>, dim3((unsigned)Nb), dim3(kPsisBlock), 0, stream, ll, S, Nb, C, t.M,
+                       t.P, t.keys, t.idx, t.xs, t.meta);
   }
   HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+
+// the three launches over ll[S][Nb][C]; rows out[3][N], this block's datums from i0
+int psis_launch(hipStream_t stream, const PsisTables& t, double* part, const double* ll, int S, int Nb, int C, int N,
+                int i0, double* out) {
+  const long long n = (long long)S * C;
+  const IcGrid g = ic_grid(S, C, Nb);
+  int rc = psis_tails(stream, t, ll, S, Nb, C);
+  if (rc) return rc;
   hipLaunchKernelGGL(psis_weights_kernel, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks), dim3(g.block), 0, stream,
-                     ll, S, Nb, C, g.chunk, sc.P, sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(),
-                     sc.meta.as<double>(), sc.part.as<double>());
+                     ll, S, Nb, C, g.chunk, t.P, t.keys, t.idx, t.xs, t.meta, part);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(psis_merge_kernel, dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, stream,
-                     sc.part.as<double>(), g.n_chunks, n, Nb, sc.meta.as<double>(), N, i0, out);
+  hipLaunchKernelGGL(psis_merge_kernel, dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, stream, part, g.n_chunks, n,
+                     Nb, t.meta, N, i0, out);
   HIP_TRY(hipGetLastError());
   return EXMC_OK;
 }
@@ -2132,7 +2152,7 @@ int psis_kind(exmc_hip_model* m, const Src& src, const double* draws, int S, int
     hipLaunchKernelGGL(pointwise_ll_range_kernel<Src>, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks),
                        dim3(g.block), lds, m->stream, src, draws, S, m->d, C, i0, nb, g.chunk, ll.as<double>());
     HIP_TRY(hipGetLastError());
-    rc = psis_launch(m->stream, sc, ll.as<double>(), S, nb, C, N, i0, out);
+    rc = psis_launch(m->stream, psis_tables(sc), sc.part.as<double>(), ll.as<double>(), S, nb, C, N, i0, out);
     if (rc) return rc;
   }
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
@@ -2293,6 +2313,76 @@ int ppc_launch(exmc_hip_model* m, const Src& src, PpcParams& P, double* y) {
   return pp_launch(m, ppc_kernel<Src>, ppc_lds_bytes(m->d), src, P);
 }
 
+// ---- LOO-PIT (exmc_loo_pit.hpp) ----
+// what a call keeps beside the scratch_bytes budget (include/exmc_hip_loo_pit.h "Memory"): the tail tables
+// of all N datums, which the second pass reads, and the block states [B][N][4]
+struct LooPitScratch {
+  CallBuf keys, idx, xs, meta, state;
+  int M = 0, P = 0, B = 0;
+  int alloc(int S, int C, int N) {
+    M = psis_tail_len((long long)S * C);
+    P = psis_pow2(M);
+    B = (C + kPpBlock - 1) / kPpBlock;
+    int rc = keys.alloc((size_t)N * P * 8);
+    if (!rc) rc = idx.alloc((size_t)N * P * 4);
+    if (!rc) rc = xs.alloc((size_t)N * P * 8);
+    if (!rc) rc = meta.alloc((size_t)N * kPsisMeta * 8);
+    if (!rc) rc = state.alloc((size_t)B * N * kLooPitFields * 8);
+    if (rc) return rc;
+    if (P <= kPsisLdsPairs && psis_tail_lds_bytes(P) > 40 * 1024)   // as PsisScratch::alloc
+      EXMC_KMAXLDS(psis_tail_kernel<true>, psis_tail_lds_bytes(P));
+    return EXMC_OK;
+  }
+  // the tables from datum i0 on: where a tail launch over the datums i0 .. writes
+  PsisTables at(int i0) const {
+    return {keys.as<uint64_t>() + (size_t)i0 * P, idx.as<uint32_t>() + (size_t)i0 * P, xs.as<double>() + (size_t)i0 * P,
+            meta.as<double>() + (size_t)i0 * kPsisMeta, M, P};
+  }
+  LooPitTables tables() const { return {keys.as<uint64_t>(), idx.as<uint32_t>(), xs.as<double>(), meta.as<double>(), P}; }
+};
+
+int loo_pit_finish(hipStream_t stream, const LooPitScratch& sc, int N, double* out) {
+  hipLaunchKernelGGL(loo_pit_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
+                     sc.state.as<double>(), sc.B, N, sc.meta.as<double>(), out);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+
+// first pass: the tails of the model's datums, in psis_kind's blocks; second pass: the fused walk; the merge
+template <class Src>
+int loo_pit_kind(exmc_hip_model* m, const Src& src, LooPitParams& P, size_t scratch_bytes, double* out) {
+  const int S = P.S, C = P.C, N = P.N;
+  const size_t per = (size_t)S * C * 8;
+  const size_t fit = scratch_bytes / per;
+  const int Nb = (int)(fit < 1 ? 1 : (fit > (size_t)N ? (size_t)N : fit));
+  LooPitScratch sc;
+  CallBuf ll;
+  int rc = sc.alloc(S, C, N);
+  if (!rc) rc = ll.alloc(per * Nb);
+  if (rc) return rc;
+  P.tab = sc.tables();
+  P.state = sc.state.as<double>();
+  const size_t lds_ll = ic_lds_bytes(m->d), lds = loo_pit_lds_bytes(m->d);
+  if (lds_ll > 64 * 1024) EXMC_KMAXLDS(pointwise_ll_range_kernel<Src>, lds_ll);
+  if (lds > 64 * 1024) EXMC_KMAXLDS(loo_pit_kernel<Src>, lds);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  for (int i0 = 0; i0 < N; i0 += Nb) {
+    const int nb = (N - i0 < Nb) ? N - i0 : Nb;
+    const IcGrid g = ic_grid(S, C, nb);
+    hipLaunchKernelGGL(pointwise_ll_range_kernel<Src>, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks),
+                       dim3(g.block), lds_ll, m->stream, src, P.draws, S, m->d, C, i0, nb, g.chunk, ll.as<double>());
+    HIP_TRY(hipGetLastError());
+    rc = psis_tails(m->stream, sc.at(i0), ll.as<double>(), S, nb, C);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(loo_pit_kernel<Src>, dim3((unsigned)sc.B), dim3(kPpBlock), lds, m->stream, src, P);
+  HIP_TRY(hipGetLastError());
+  rc = loo_pit_finish(m->stream, sc, N, out);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the kernels: before the scratch is freed
+}
+
 #endif
 
 #ifdef EXMC_GEN_POINTWISE
@@ -2451,7 +2541,8 @@ int exmc_hip_psis_stats_from_ll(int device, const double* ll_dev, int n_draws, i
   PsisScratch sc;
   rc = sc.alloc(n_draws, n_chains, n_data);
   if (rc) return rc;
-  rc = psis_launch((hipStream_t)0, sc, ll_dev, n_draws, n_data, n_chains, n_data, 0, out_dev);
+  rc = psis_launch((hipStream_t)0, psis_tables(sc), sc.part.as<double>(), ll_dev, n_draws, n_data, n_chains, n_data, 0,
+                   out_dev);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize((hipStream_t)0));
   return EXMC_OK;
@@ -2511,7 +2602,7 @@ int pp_check(exmc_hip_model* m, const char* what, const exmc_hip_predictive_opts
 #endif
 }
 
-// the fields PredictiveParams and PpcParams share
+// the fields PredictiveParams, PpcParams and LooPitParams share
 template <class Params>
 void pp_fill(Params& P, exmc_hip_model* m, const exmc_hip_predictive_opts& o, const double* draws_dev, int n_draws,
              int d, int n_chains) {
@@ -2771,6 +2862,74 @@ int exmc_hip_ppc_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const doubl
   if (tstat) transpose_trace_vec(sc.host(s_ts), tstat, n_draws, kPpcStats, n_chains);
 #endif
   return rc;
+}
+
+// ---- LOO-PIT (include/exmc_hip_loo_pit.h; loo_pit_kernel, exmc_loo_pit.hpp) ----------------------------
+int exmc_hip_loo_pit(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws_dev, int n_draws, int d,
+                     int n_chains, size_t scratch_bytes, double* out_dev) {
+  const long long n = (long long)n_draws * n_chains;
+  int rc = pp_check(m, "loo-pit", o, draws_dev, n_draws, d, n_chains,
+                    !out_dev || o.resume || n < 2 || n > 0x7FFFFFFFLL);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)scratch_bytes;
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  LooPitParams P;
+  pp_fill(P, m, o, draws_dev, n_draws, d, n_chains);
+  const size_t scratch = scratch_bytes ? scratch_bytes : (size_t)EXMC_LOO_PIT_DEFAULT_SCRATCH;
+  rc = ic_with_src(m, [&](const auto& src) { return loo_pit_kind(m, src, P, scratch, out_dev); });
+#endif
+  return rc;
+}
+
+int exmc_hip_loo_pit_host(exmc_hip_model* m, exmc_hip_predictive_opts o, const double* draws, int n_draws, int d,
+                          int n_chains, size_t scratch_bytes, double* out) {
+  const long long n = (long long)n_draws * n_chains;
+  int rc = pp_check(m, "loo-pit", o, draws, n_draws, d, n_chains, !out || o.resume || n < 2 || n > 0x7FFFFFFFLL);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)scratch_bytes;
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t n_out = (size_t)kLooPitRows * (size_t)ic_n_data(m);
+  Scratch sc;
+  const auto s_out = sc.take<double>(n_out);   // [4][N]
+  rc = sc.alloc_with_trace(draws, n_draws, d, n_chains);
+  if (!rc) rc = exmc_hip_loo_pit(m, o, sc.trace(), n_draws, d, n_chains, scratch_bytes, sc.dev(s_out));
+  if (!rc) rc = sc.download();
+  if (rc) return rc;
+  std::copy(sc.host(s_out), sc.host(s_out) + n_out, out);
+#endif
+  return rc;
+}
+
+int exmc_hip_loo_pit_from_ll(int device, const double* ll_dev, const double* yrep_dev, const double* y_dev,
+                             int n_draws, int n_data, int n_chains, double* out_dev) {
+  if (!ll_dev || !yrep_dev || !y_dev || !out_dev || n_draws < 1 || n_data < 1 || n_chains < 1 ||
+      (long long)n_draws * n_chains < 2)
+    return fail(EXMC_ERR_BADARG, "loo-pit: bad arguments");
+  int rc = select_device(device);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  return fail(EXMC_ERR_UNSUPPORTED, "loo-pit: use libexmc_hip.so for the model-free reduction");
+#else
+  if ((long long)n_draws * n_chains > kPsisMaxSamples)
+    return fail(EXMC_ERR_BADARG, "loo-pit: more than 2^31 - 1 pooled samples");
+  const int S = n_draws, N = n_data, C = n_chains;
+  const hipStream_t stream = (hipStream_t)0;
+  LooPitScratch sc;
+  rc = sc.alloc(S, C, N);
+  if (!rc) rc = psis_tails(stream, sc.at(0), ll_dev, S, N, C);
+  if (rc) return rc;
+  hipLaunchKernelGGL(loo_pit_ll_kernel, dim3((unsigned)sc.B, (unsigned)((N + kPpBlock - 1) / kPpBlock)), dim3(kPpBlock),
+                     0, stream, ll_dev, yrep_dev, y_dev, S, N, C, sc.tables(), sc.state.as<double>());
+  HIP_TRY(hipGetLastError());
+  rc = loo_pit_finish(stream, sc, N, out_dev);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(stream));
+  return EXMC_OK;
+#endif
 }
 
 }  // extern "C"

@@ -243,4 +243,5 @@ __global__ void __launch_bounds__(kNutsBlock) find_eps_kernel(FindEpsParams P,
 #ifndef EXMC_ONLY_CUSTOM            // a generated model's plug-in carries no predictive kernels
 #include "exmc_predictive.hpp"      // predictive_kernel: Exmc.Predictive, one chain's generator per lane
 #include "exmc_ppc.hpp"             // ppc_kernel: posterior predictive checks, the replicates reduced in place
+#include "exmc_loo_pit.hpp"         // loo_pit_kernel: PSIS-LOO-PIT, the replicates weighted where they are drawn
 #endif

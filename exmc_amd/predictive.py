@@ -6,6 +6,9 @@ device kernel.
     as_trace(yrep, names)                          -> {name: [C][S] numpy}, the reference's map
     ppc(compiled, draws, seed=0)                   -> posterior predictive checks of the same replicates,
                                                       reduced on the device without the matrix
+    loo_pit(compiled, draws, seed=0)               -> PSIS-LOO-PIT: the same replicates under the smoothed
+                                                      leave-one-out weights of PSIS-LOO
+    loo_pit_from_pointwise(ll, yrep, y)            -> the same from matrices the caller made
 
 The unit is the datum of a built-in kind, as in exmc_amd/model_comparison.py (include/exmc_hip_compare.h):
 one y_i, one return r_t, in the handle's datum order (`names` says which is which). `draws` is the device
@@ -20,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .diagnostics import _device_trace, _ordered_after_torch
-from .model_comparison import _datum_order, datum_names, n_data
+from .model_comparison import _check_samples, _datum_order, _ll_tensor, datum_names, k_threshold, n_data
 
 # posterior_predictive refuses matrices above this many bytes: posterior_predictive_blocks walks the draws
 PREDICTIVE_MAX_BYTES = 2 << 30
@@ -137,3 +140,63 @@ def ppc(compiled, draws, seed=0, chain_lo=0, tstat=False):
     if tstat:
         out["tstat"] = ts
     return out
+
+
+def _loo_pit_result(out, n, names):
+    """the rows of include/exmc_hip_loo_pit.h as a dict, k_threshold and n_high_k as psis_loo forms them"""
+    r = dict(names=list(names), **{k: out[i].copy() for i, k in enumerate(_lib.LOO_PIT_ROWS)})
+    thr = k_threshold(n)
+    r["k_threshold"] = thr
+    r["n_high_k"] = int(np.sum(~(out[3] <= thr)))   # NaN (a degenerate fit, a non-finite term) counts
+    return r
+
+
+def loo_pit(compiled, draws, seed=0, chain_lo=0, scratch_bytes=0):
+    """PSIS-LOO-PIT (include/exmc_hip_loo_pit.h, DESIGN.md "LOO-PIT"): the probability integral transform
+    of every observation under its leave-one-out predictive distribution. The replicates are those of
+    posterior_predictive at the same seed and chain_lo, each weighted with the Pareto-smoothed importance
+    weight of its sample, as psis_loo forms it; neither matrix is kept. A dict: `names` (the datums in the
+    handle's order, as posterior_predictive returns them); per datum [N] numpy `p_lt` and `p_eq` (the
+    weighted share of replicates below and equal to the observation), `pit` = p_lt + 0.5 p_eq and `k`, the
+    datum's Pareto k (+inf where nothing was smoothed); `k_threshold` and `n_high_k`, the number of datums
+    whose k is not at or below it: nothing vouches for their PIT. A datum with a non-finite term has NaN in
+    all four. The weights pool all chains of the call: there is no sharding, chain_lo only seeds the
+    generators. scratch_bytes bounds the pointwise matrix of the first pass (0: the library's default,
+    8 GiB); the result does not depend on it."""
+    import torch
+    N = n_data(compiled)
+    x = _device_trace(compiled, draws)
+    S, d, Cn = x.shape
+    out = torch.empty((len(_lib.LOO_PIT_ROWS), N), dtype=torch.float64, device=x.device)
+    opts = _lib.PredictiveOpts(int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_lo), 0)
+    _ordered_after_torch(x)
+    compiled.check(compiled.L.exmc_hip_loo_pit(compiled.h, opts, x.data_ptr(), S, d, Cn, int(scratch_bytes),
+                                               out.data_ptr()))
+    torch.cuda.synchronize(x.device)
+    return _loo_pit_result(out.cpu().numpy(), S * Cn, _names(compiled, N))
+
+
+def loo_pit_from_pointwise(ll, yrep, y, names=None, device=None):
+    """loo_pit from a pointwise matrix ll [S][N][C], the replicates yrep [S][N][C] and the observations
+    y [N] (device tensors or host arrays): for models whose terms and replicates the caller made"""
+    import torch
+    x = _ll_tensor(ll, device)
+    v = _ll_tensor(yrep, x.device.index)
+    S, N, Cn = x.shape
+    if N < 1:
+        raise ValueError("No observations for LOO-PIT computation")
+    if tuple(v.shape) != (S, N, Cn) or v.device != x.device:
+        raise ValueError("yrep must be [S][N][C] like ll, on the same device")
+    _check_samples(S, Cn)
+    if isinstance(y, torch.Tensor):
+        yd = y.to(device=x.device, dtype=torch.float64).contiguous()
+    else:
+        yd = torch.from_numpy(np.ascontiguousarray(np.asarray(y, dtype=np.float64))).to(x.device)
+    if tuple(yd.shape) != (N,):
+        raise ValueError("y must hold one observation per datum")
+    out = torch.empty((len(_lib.LOO_PIT_ROWS), N), dtype=torch.float64, device=x.device)
+    _ordered_after_torch(x)
+    _lib.check(_lib.load().exmc_hip_loo_pit_from_ll(x.device.index, x.data_ptr(), v.data_ptr(), yd.data_ptr(), S, N, Cn,
+                                                    out.data_ptr()))
+    torch.cuda.synchronize(x.device)
+    return _loo_pit_result(out.cpu().numpy(), S * Cn, names if names is not None else list(range(N)))
