@@ -28,6 +28,15 @@ namespace exmc {
 
 constexpr uint64_t kMask58 = (1ULL << 58) - 1;
 
+// Timing only ("Round 12"): the pieces of that round, each of which builds alone
+// for its counter run. 1: the trace row in two stores (exmc_nuts.hpp nuts_kernel, M::kPackedTrace);
+// 2: the long-way normal of the window draw as one straight-line wedge attempt (normal_wedge_once);
+// 4: the sums that start from zero without the leading s_nop (the row_seqsum*_zero forms). Same bits
+// with any set.
+#ifndef EXMC_FIXED_PART_PIECES
+#define EXMC_FIXED_PART_PIECES 7
+#endif
+
 // ---- IEEE f64 division without the range instructions (exmc_detmath.h: exmc_div_core) ----
 // The short sequence is bit-identical to the compiler's full f64 division when both operands
 // have magnitudes in [2^-380, 2^380): neither operand nor quotient is then zero, denormal or
@@ -383,20 +392,22 @@ inline constexpr bool kSeqSum = (G == 16 && D <= 12);
 #define EXMC_LANES_10(S) EXMC_LANES_9(S) S(9)
 #define EXMC_LANES_11(S) EXMC_LANES_10(S) S(10)
 #define EXMC_LANES_12(S) EXMC_LANES_11(S) S(11)
-// the asm statement for NL lanes, chosen at compile time
-#define EXMC_SEQSUM_ASM(SEQ, OUTS, INS)                                                        \
-  if constexpr (NL == 1) __asm__("s_nop 1\n\t" EXMC_LANES_1(SEQ) : OUTS : INS);                \
-  else if constexpr (NL == 2) __asm__("s_nop 1\n\t" EXMC_LANES_2(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 3) __asm__("s_nop 1\n\t" EXMC_LANES_3(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 4) __asm__("s_nop 1\n\t" EXMC_LANES_4(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 5) __asm__("s_nop 1\n\t" EXMC_LANES_5(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 6) __asm__("s_nop 1\n\t" EXMC_LANES_6(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 7) __asm__("s_nop 1\n\t" EXMC_LANES_7(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 8) __asm__("s_nop 1\n\t" EXMC_LANES_8(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 9) __asm__("s_nop 1\n\t" EXMC_LANES_9(SEQ) : OUTS : INS);           \
-  else if constexpr (NL == 10) __asm__("s_nop 1\n\t" EXMC_LANES_10(SEQ) : OUTS : INS);         \
-  else if constexpr (NL == 11) __asm__("s_nop 1\n\t" EXMC_LANES_11(SEQ) : OUTS : INS);         \
-  else __asm__("s_nop 1\n\t" EXMC_LANES_12(SEQ) : OUTS : INS);
+// the asm statement for NL lanes, chosen at compile time; HEAD is what stands in front of the chain
+#define EXMC_SEQSUM_ASM_H(HEAD, SEQ, OUTS, INS)                                              \
+  if constexpr (NL == 1) __asm__(HEAD EXMC_LANES_1(SEQ) : OUTS : INS);                         \
+  else if constexpr (NL == 2) __asm__(HEAD EXMC_LANES_2(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 3) __asm__(HEAD EXMC_LANES_3(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 4) __asm__(HEAD EXMC_LANES_4(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 5) __asm__(HEAD EXMC_LANES_5(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 6) __asm__(HEAD EXMC_LANES_6(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 7) __asm__(HEAD EXMC_LANES_7(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 8) __asm__(HEAD EXMC_LANES_8(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 9) __asm__(HEAD EXMC_LANES_9(SEQ) : OUTS : INS);                    \
+  else if constexpr (NL == 10) __asm__(HEAD EXMC_LANES_10(SEQ) : OUTS : INS);                  \
+  else if constexpr (NL == 11) __asm__(HEAD EXMC_LANES_11(SEQ) : OUTS : INS);                  \
+  else __asm__(HEAD EXMC_LANES_12(SEQ) : OUTS : INS);
+// the two wait states between a VALU write of a term and its DPP read
+#define EXMC_NOP2 "s_nop 1\n\t"
 #define EXMC_COMMA ,
 
 // 1.0 as a vector-register operand (the DPP form of v_fmac_f64 takes no literal): a plain constant,
@@ -408,19 +419,19 @@ template <int NL>
 __device__ __forceinline__ void row_seqsum(double& a0, double v0) {
   static_assert(NL >= 1 && NL <= 12, "lanes of one DPP row, where the chain beats the butterfly");
   const double one = seq_one();
-  EXMC_SEQSUM_ASM(EXMC_SEQ1, [a0] "+v"(a0), [v0] "v"(v0) EXMC_COMMA [one] "v"(one))
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ1, [a0] "+v"(a0), [v0] "v"(v0) EXMC_COMMA [one] "v"(one))
 }
 template <int NL>
 __device__ __forceinline__ void row_seqsum(double& a0, double& a1, double v0, double v1) {
   const double one = seq_one();
-  EXMC_SEQSUM_ASM(EXMC_SEQ2, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1),
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ2, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1),
                   [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [one] "v"(one))
 }
 template <int NL>
 __device__ __forceinline__ void row_seqsum(double& a0, double& a1, double& a2, double v0, double v1,
                                            double v2) {
   const double one = seq_one();
-  EXMC_SEQSUM_ASM(EXMC_SEQ3, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ3, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
                   [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [v2] "v"(v2) EXMC_COMMA [one] "v"(one))
 }
 // The lane-range form: a_j <- a_j + v_j[lane I0] + ... + v_j[lane I0 + NL - 1], the same chain in one
@@ -437,7 +448,7 @@ __device__ __forceinline__ void row_seqsum_lanes(double& a0, double& a1, double&
                                                  double v2) {
   static_assert(I0 >= 0 && NL >= 1 && NL <= 12 && I0 + NL <= 16, "a lane range of one DPP row");
   const double one = seq_one();
-  EXMC_SEQSUM_ASM(EXMC_SEQ3R, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ3R, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
                   [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [v2] "v"(v2) EXMC_COMMA [one] "v"(one) EXMC_COMMA
                   EXMC_LANE_R(0) EXMC_COMMA EXMC_LANE_R(1) EXMC_COMMA EXMC_LANE_R(2) EXMC_COMMA EXMC_LANE_R(3) EXMC_COMMA
                   EXMC_LANE_R(4) EXMC_COMMA EXMC_LANE_R(5) EXMC_COMMA EXMC_LANE_R(6) EXMC_COMMA EXMC_LANE_R(7) EXMC_COMMA
@@ -450,6 +461,40 @@ __device__ __forceinline__ void row_seqsum_lanes(double& a0, double& a1, double&
 #ifndef EXMC_ROW_SUM_PIECES
 #define EXMC_ROW_SUM_PIECES 7
 #endif
+// The chains above where EVERY accumulator starts at +0.0: the zeroing is the block's own first
+// instructions. The leading s_nop 1 of the other blocks stands for the two wait states between a VALU
+// write of a term and its DPP read; two or more independent v_mov_b64 in front of the first fmac are
+// those wait states, so the nop goes: one issue slot per block. The accumulators are written before
+// the terms are read, hence early-clobber outputs. Same chain from the same +0.0, same bits.
+#define EXMC_ZERO_B(A) "v_mov_b64 %[" #A "], 0\n\t"
+inline constexpr bool kZeroInBlock = (EXMC_FIXED_PART_PIECES & 4) != 0;
+template <int NL>
+__device__ __forceinline__ void row_seqsum_zero(double& a0, double& a1, double v0, double v1) {
+  if constexpr (kZeroInBlock) {
+    const double one = seq_one();
+    EXMC_SEQSUM_ASM_H(EXMC_ZERO_B(a0) EXMC_ZERO_B(a1), EXMC_SEQ2, [a0] "=&v"(a0) EXMC_COMMA [a1] "=&v"(a1),
+                      [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [one] "v"(one))
+  } else {
+    a0 = a1 = 0.0;
+    row_seqsum<NL>(a0, a1, v0, v1);
+  }
+}
+template <int I0, int NL>
+__device__ __forceinline__ void row_seqsum_lanes_zero(double& a0, double& a1, double& a2, double v0, double v1,
+                                                      double v2) {
+  if constexpr (kZeroInBlock) {
+    const double one = seq_one();
+    EXMC_SEQSUM_ASM_H(EXMC_ZERO_B(a0) EXMC_ZERO_B(a1) EXMC_ZERO_B(a2), EXMC_SEQ3R,
+                      [a0] "=&v"(a0) EXMC_COMMA [a1] "=&v"(a1) EXMC_COMMA [a2] "=&v"(a2),
+                      [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [v2] "v"(v2) EXMC_COMMA [one] "v"(one) EXMC_COMMA
+                      EXMC_LANE_R(0) EXMC_COMMA EXMC_LANE_R(1) EXMC_COMMA EXMC_LANE_R(2) EXMC_COMMA EXMC_LANE_R(3) EXMC_COMMA
+                      EXMC_LANE_R(4) EXMC_COMMA EXMC_LANE_R(5) EXMC_COMMA EXMC_LANE_R(6) EXMC_COMMA EXMC_LANE_R(7) EXMC_COMMA
+                      EXMC_LANE_R(8) EXMC_COMMA EXMC_LANE_R(9) EXMC_COMMA EXMC_LANE_R(10) EXMC_COMMA EXMC_LANE_R(11))
+  } else {
+    a0 = a1 = a2 = 0.0;
+    row_seqsum_lanes<I0, NL>(a0, a1, a2, v0, v1, v2);
+  }
+}
 // ---- a dense D x D matrix against a vector held one entry per lane (row layout of a 16-lane
 // chain group): lane i keeps row i of the matrix in registers and
 //     acc = fma(x[lane j], c[j], acc)   for j = 0 .. NL-1, from 0.0
@@ -461,7 +506,7 @@ __device__ __forceinline__ double row_matvec(double x, const double (&c)[NL]) {
   static_assert(NL >= 1 && NL <= 12, "lanes of one DPP row");
   double acc = 0.0;
 #define EXMC_MV_C(I) [c##I] "v"(c[(I) < NL ? (I) : 0])
-  EXMC_SEQSUM_ASM(EXMC_MV1, [acc] "+v"(acc),
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_MV1, [acc] "+v"(acc),
                   [x] "v"(x) EXMC_COMMA EXMC_MV_C(0) EXMC_COMMA EXMC_MV_C(1) EXMC_COMMA EXMC_MV_C(2) EXMC_COMMA
                   EXMC_MV_C(3) EXMC_COMMA EXMC_MV_C(4) EXMC_COMMA EXMC_MV_C(5) EXMC_COMMA EXMC_MV_C(6) EXMC_COMMA
                   EXMC_MV_C(7) EXMC_COMMA EXMC_MV_C(8) EXMC_COMMA EXMC_MV_C(9) EXMC_COMMA EXMC_MV_C(10) EXMC_COMMA
@@ -479,7 +524,7 @@ __device__ __forceinline__ void row_outer_acc(double (&m)[NL], double x, double 
 #pragma unroll
   for (int j = 0; j < 12; j++) pad[j] = (j < NL) ? m[j < NL ? j : 0] : 0.0;
 #define EXMC_OUTER_M(I) [m##I] "+v"(pad[I])
-  EXMC_SEQSUM_ASM(EXMC_OUTER1,
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_OUTER1,
                   EXMC_OUTER_M(0) EXMC_COMMA EXMC_OUTER_M(1) EXMC_COMMA EXMC_OUTER_M(2) EXMC_COMMA EXMC_OUTER_M(3) EXMC_COMMA
                   EXMC_OUTER_M(4) EXMC_COMMA EXMC_OUTER_M(5) EXMC_COMMA EXMC_OUTER_M(6) EXMC_COMMA EXMC_OUTER_M(7) EXMC_COMMA
                   EXMC_OUTER_M(8) EXMC_COMMA EXMC_OUTER_M(9) EXMC_COMMA EXMC_OUTER_M(10) EXMC_COMMA EXMC_OUTER_M(11),
@@ -501,12 +546,30 @@ __device__ __forceinline__ double row_bcast_f64(double x) {
 template <int NL>
 __device__ __forceinline__ void row_seqsum6(double (&a)[6], const double (&v)[6]) {
   const double one = seq_one();
-  EXMC_SEQSUM_ASM(EXMC_SEQ6,
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ6,
                   [a0] "+v"(a[0]) EXMC_COMMA [a1] "+v"(a[1]) EXMC_COMMA [a2] "+v"(a[2]) EXMC_COMMA
                   [a3] "+v"(a[3]) EXMC_COMMA [a4] "+v"(a[4]) EXMC_COMMA [a5] "+v"(a[5]),
                   [v0] "v"(v[0]) EXMC_COMMA [v1] "v"(v[1]) EXMC_COMMA [v2] "v"(v[2]) EXMC_COMMA
                   [v3] "v"(v[3]) EXMC_COMMA [v4] "v"(v[4]) EXMC_COMMA [v5] "v"(v[5]) EXMC_COMMA
                   [one] "v"(one))
+}
+// ... from +0.0 in all six (see row_seqsum_zero)
+template <int NL>
+__device__ __forceinline__ void row_seqsum6_zero(double (&a)[6], const double (&v)[6]) {
+  if constexpr (kZeroInBlock) {
+    const double one = seq_one();
+    EXMC_SEQSUM_ASM_H(EXMC_ZERO_B(a0) EXMC_ZERO_B(a1) EXMC_ZERO_B(a2) EXMC_ZERO_B(a3) EXMC_ZERO_B(a4) EXMC_ZERO_B(a5),
+                      EXMC_SEQ6,
+                      [a0] "=&v"(a[0]) EXMC_COMMA [a1] "=&v"(a[1]) EXMC_COMMA [a2] "=&v"(a[2]) EXMC_COMMA
+                      [a3] "=&v"(a[3]) EXMC_COMMA [a4] "=&v"(a[4]) EXMC_COMMA [a5] "=&v"(a[5]),
+                      [v0] "v"(v[0]) EXMC_COMMA [v1] "v"(v[1]) EXMC_COMMA [v2] "v"(v[2]) EXMC_COMMA
+                      [v3] "v"(v[3]) EXMC_COMMA [v4] "v"(v[4]) EXMC_COMMA [v5] "v"(v[5]) EXMC_COMMA
+                      [one] "v"(one))
+  } else {
+#pragma unroll
+    for (int j = 0; j < 6; j++) a[j] = 0.0;
+    row_seqsum6<NL>(a, v);
+  }
 }
 
 // value held by lane `src` (0..G-1) of this lane's group
@@ -782,6 +845,46 @@ struct Math {
   }
 };
 
+// The long way of normal_s for a word normal_fast has rejected, its common case without a loop: what
+// the first pass of rng_normal_impl does behind the failed table test. w is the rejected (scrambled)
+// word, r the state in FRONT of it. A layer other than the tail (idx != 0) draws one uniform and
+// accepts x where the wedge test holds -- exp(-0.5 x^2) by the exp_le0 core: R >= ki[idx] > 0, so
+// x != 0 and the argument is negative, where exp_le0 is exmc_exp bit for bit (tests/test_detmath_*)
+// -- and the draw has consumed two words. A wedge that rejects goes on as the loop of rng_normal_impl
+// does, with a fresh draw behind the uniform; the tail takes rng_normal_counted from r as before (it
+// draws w again). The variate, the state behind the draw and the words it consumed are those of
+// rng_normal_counted(r, ...) in every case.
+template <bool kVreg>
+__device__ __forceinline__ double normal_wedge_once(uint64_t w, Rng& r, const ZigTables& zt, double nor_r,
+                                                    int& words) {
+  const int sign = (int)((w >> 6) & 1);
+  const uint64_t R = w >> 7;
+  const int idx = (int)(R & 255);
+  double x = (double)R * zt.wi[idx];
+  if (sign) x = -x;
+  Rng r2 = r;
+  rng_advance(r2);   // behind the rejected word
+  const double u0 = rng_uniform(r2);
+  const int ix = (idx != 0) ? idx : 1;   // (the tail's loads stay inside the table; their result is not used)
+  const double fi2 = zt.fi[ix];
+  const bool acc = (idx != 0) && ((zt.fi[ix - 1] - fi2) * u0 + fi2 < Math<kVreg>::exp_le0(-0.5 * x * x));
+  double z = x;
+  int n = 2;
+  if (__any(acc ? 0 : 1) != 0) {
+    if (!acc) {
+      // a wedge that rejects starts the draw again behind its uniform (rng_normal_impl's loop, second
+      // pass on); the tail's own loop draws from behind the rejected word, so it starts over from r
+      Rng rr = (idx != 0) ? r2 : r;
+      n = (idx != 0) ? 2 : 0;
+      z = rng_normal_counted(rr, zt, nor_r, n);
+      r2 = rr;
+    }
+  }
+  r = r2;
+  words += n;
+  return z;
+}
+
 // ---- 64-lane sums as a reduce-scatter (one chain per wavefront) ----
 // group_allsum_n<64, N> moves every one of its N values through all six butterfly stages: 6 N
 // exchanges and adds. The sum tree of a value does not care WHICH lane adds a pair, so the first
@@ -979,8 +1082,7 @@ __device__ __forceinline__ bool uturn(const double (&rho)[DPL], const double (&p
   double s[2];
   if constexpr (kSeqSum<G, D>) {
     const double v = rho[0] * im[0];
-    s[0] = s[1] = 0.0;
-    row_seqsum<D>(s[0], s[1], v * pa[0], v * pb[0]);
+    row_seqsum_zero<D>(s[0], s[1], v * pa[0], v * pb[0]);
   } else {
     uturn_partials<DPL>(rho, pa, pb, im, valid, s[0], s[1]);
     if constexpr (G == 64 && (kLds || EXMC_XROW_PERMLANE)) {
@@ -1014,9 +1116,7 @@ __device__ __forceinline__ void uturn3(const double (&r1)[DPL], const double (&a
   if constexpr (kSeqSum<G, D>) {
     const double v1 = r1[0] * im[0], v2 = r2[0] * im[0], v3 = r3[0] * im[0];
     const double t[6] = {v1 * a1[0], v1 * b1[0], v2 * a2[0], v2 * b2[0], v3 * a3[0], v3 * b3[0]};
-#pragma unroll
-    for (int j = 0; j < 6; j++) s[j] = 0.0;
-    row_seqsum6<D>(s, t);
+    row_seqsum6_zero<D>(s, t);
   } else {
     uturn_partials<DPL>(r1, a1, b1, im, valid, s[0], s[1]);
     uturn_partials<DPL>(r2, a2, b2, im, valid, s[2], s[3]);

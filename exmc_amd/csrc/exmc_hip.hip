@@ -69,6 +69,28 @@ hipError_t print_sections(const char* what, double ms) {
   if (h[10])
     fprintf(stderr, "[exmc prof]   integrator wave: %llu units, %.1f cycles/unit compute, %.1f barrier wait, %.1f other\n",
             h[10], (double)h[11] / (double)h[10], (double)h[12] / (double)h[10], (double)h[13] / (double)h[10]);
+#if EXMC_PROFILE_SECTIONS >= 2
+  // the marks inside "transition start" (= 2) or inside the trace sink (= 3): exmc_nuts.hpp g_prof_sub
+  unsigned long long s[8], sz[8] = {0};
+  e = hipMemcpyFromSymbol(s, HIP_SYMBOL(g_prof_sub), sizeof(s));
+  if (e != hipSuccess) return e;
+  e = hipMemcpyToSymbol(HIP_SYMBOL(g_prof_sub), sz, sizeof(sz));
+  if (e != hipSuccess) return e;
+#if EXMC_PROFILE_SECTIONS == 2
+  static const char* sn[5] = {"start: window draw", "start: long-way rounds", "start: stepping loop",
+                              "start: momentum_from_variates", "start: mass_ke"};
+  const int ns = 5;
+#else
+  static const char* sn[3] = {"done: draws store", "done: stat stores", "done: cursor steps"};
+  const int ns = 3;
+#endif
+  for (int i = 0; i < ns; i++)
+    if (h[9])
+      fprintf(stderr, "[exmc prof]   %-30s %6.2f%%  %8.1f cycles/pass\n", sn[i],
+              100.0 * (double)s[i] / (double)tot, (double)s[i] / (double)h[9]);
+  if (EXMC_PROFILE_SECTIONS == 2)
+    fprintf(stderr, "[exmc prof]   long-way rounds (sum over waves) %llu, wave-transitions %llu\n", s[5], s[6]);
+#endif
   return hipSuccess;
 }
 #endif

@@ -106,6 +106,10 @@ struct ModelDefaults {
   // kept one per lane of the group's DPP row (exmc_nuts.hpp RngRowWindow). tree_prefix takes its ten
   // uniforms from it and the next transition's momentum its normals; same words, same bits.
   static constexpr bool kRngWindow = false;
+  // The sampling kernel writes a trace row in two stores: the draw and the three 8-byte statistics in
+  // one, the three 4-byte statistics in the other, each statistic from a spare lane of the group
+  // (exmc_nuts.hpp nuts_kernel). Needs one dimension a lane and six lanes of the group past D.
+  static constexpr bool kPackedTrace = false;
 };
 
 // the dynamic LDS of the running kernel (every extern __shared__ array names the same base)
@@ -157,6 +161,8 @@ struct EightSchools : ModelDefaults {
   static constexpr bool kTreePrefix = (G == 16);
   // ... and one generator walk per transition ("Round 10")
   static constexpr bool kRngWindow = (G == 16);
+  // the trace row in two stores ("Round 12")
+  static constexpr bool kPackedTrace = (G == 16);
   using MM = Math<kVregMath>;
   using Consts = EightSchoolsConsts;
   struct Lane {
@@ -230,10 +236,10 @@ struct EightSchools : ModelDefaults {
     const double Lk = (-0.5 * (z * z)) - ln.lsg[0];
     const double Ak = a;
     const double Bk = a * th;
-    double lik = 0.0, sa = 0.0, sb = 0.0;
+    double lik = 0.0, sa = 0.0, sb = 0.0;   // (row_seqsum_lanes_zero sets them itself)
     // the three likelihood sums over the lanes that hold a term, 2 .. 9: the other lanes' values are
     // not read, so they need no select (the full chain added +0.0 for lanes 0 and 1: the same bits)
-    if constexpr (kThetaLanes) row_seqsum_lanes<2, D - 2>(lik, sa, sb, Lk, Ak, Bk);
+    if constexpr (kThetaLanes) row_seqsum_lanes_zero<2, D - 2>(lik, sa, sb, Lk, Ak, Bk);
     else row_seqsum<D>(lik, sa, sb, isth ? Lk : 0.0, isth ? Ak : 0.0, isth ? Bk : 0.0);
     // hyper-parameter lanes
     const double x = l0 ? (mu - 0.0) : tau;
@@ -1726,6 +1732,7 @@ struct RowDenseModel : M {
   static constexpr bool kOuterLogPair = false;
   static constexpr bool kTreePrefix = false;   // likewise (exmc_nuts.hpp tree_prefix)
   static constexpr bool kRngWindow = false;    // (the window is built inside tree_prefix)
+  static constexpr bool kPackedTrace = false;  // (the trace row in two stores: the diagonal-mass kernels only)
   static_assert(M::DPL == 1 && M::D <= 12, "row layout: one dimension per lane, D <= 12");
 };
 

@@ -77,7 +77,36 @@ __device__ unsigned long long g_prof[16];
   if ((threadIdx.x & 63) == 0) {                                               \
     for (int i_ = 0; i_ < 4; i_++) atomicAdd(&g_prof[10 + i_], (unsigned long long)iprof_[i_]); \
   }
+// EXMC_PROFILE_SECTIONS = 2 / 3: marks inside "transition start" / inside the trace sink of "transition
+// done" as well ("Round 12"). g_prof_sub, = 2: [0] the window draw without its
+// long-way rounds, [1] the long-way rounds, [2] the stepping loop, [3] momentum_from_variates, [4]
+// mass_ke, [5] long-way rounds (a count per wave); what is left of the section stays in g_prof[0].
+// = 3: [0] behind the draws' store, [1] behind the statistics' stores, [2] behind the cursor steps; these
+// clocks are part of g_prof[6] too.
+__device__ unsigned long long g_prof_sub[8];
+#define EXMC_SUBPROF_DECL long long sub_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#define EXMC_SUBPROF_FLUSH                                                     \
+  if ((threadIdx.x & 63) == 0) {                                               \
+    for (int i_ = 0; i_ < 8; i_++) atomicAdd(&g_prof_sub[i_], (unsigned long long)sub_[i_]); \
+  }
+#if EXMC_PROFILE_SECTIONS == 2
+#define EXMC_SUBPROF(i) { const long long n_ = clock64(); sub_[i] += n_ - prof_t_; prof_t_ = n_; }
 #else
+#define EXMC_SUBPROF(i)
+#endif
+#if EXMC_PROFILE_SECTIONS == 3
+#define EXMC_SINKPROF_T0 long long sink_t_ = clock64();
+#define EXMC_SINKPROF(i) { const long long n_ = clock64(); sub_[i] += n_ - sink_t_; sink_t_ = n_; }
+#else
+#define EXMC_SINKPROF_T0
+#define EXMC_SINKPROF(i)
+#endif
+#else
+#define EXMC_SUBPROF_DECL
+#define EXMC_SUBPROF_FLUSH
+#define EXMC_SUBPROF(i)
+#define EXMC_SINKPROF_T0
+#define EXMC_SINKPROF(i)
 #define EXMC_IPROF_DECL
 #define EXMC_IPROF(i)
 #define EXMC_IPROF_COUNT
@@ -757,7 +786,9 @@ struct RngRowWindow {
 // a group that is done.
 template <class M, int G, int W>
 __device__ __forceinline__ void draw_momentum_window(const NutsLane<M, G>& L, const RngRowWindow<W>& win,
-                                                     Rng& rng, double (&z)[M::DPL], int& left) {
+                                                     Rng& rng, double (&z)[M::DPL], int& left,
+                                                     long long* prof_long = nullptr) {
+  // (prof_long: the EXMC_PROFILE_SECTIONS = 2 build's clocks and count of the long-way rounds)
   constexpr int D = M::D;
   static_assert(G == 16 && M::DPL == 1, "a group is one DPP row with one dimension a lane");
   static_assert(W >= D + 2, "the state behind the momentum at shift 0");
@@ -781,13 +812,20 @@ __device__ __forceinline__ void draw_momentum_window(const NutsLane<M, G>& L, co
     const int j = (gm != 0) ? (__ffsll((long long)gm) - 1) : D;   // first draw that needs the long way
     if (m == 0) break;
     flat = false;
+#if EXMC_PROFILE_SECTIONS == 2
+    const long long long_t0 = clock64();
+#endif
     if (j < D) {
       const int pj = 1 + j + shift;   // <= D + kMaxShift < W
       Rng rj;
       rj.a = win.at(pj - 1);
       rj.b = win.at(pj);
       int words = 0;
-      zz = rng_normal_counted(rj, L.zt, L.nor_r, words);
+      // (the rejected word again: one scramble, instead of fetching draw j's from its lane)
+      if constexpr ((EXMC_FIXED_PART_PIECES & 2) != 0)
+        zz = normal_wedge_once<M::kVregMath>(rng_scramble(rj.b), rj, L.zt, L.nor_r, words);
+      else
+        zz = rng_normal_counted(rj, L.zt, L.nor_r, words);
       z[0] = (rank == j) ? zz : z[0];
       shift += words - 1;
       pos = j + 1;
@@ -800,6 +838,12 @@ __device__ __forceinline__ void draw_momentum_window(const NutsLane<M, G>& L, co
     } else {
       pos = D;
     }
+#if EXMC_PROFILE_SECTIONS == 2
+    if (prof_long) {
+      prof_long[0] += clock64() - long_t0;
+      prof_long[1] += 1;
+    }
+#endif
   }
   if (flat) {
     rng = win.template state<D + 1>();
@@ -1753,8 +1797,12 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
   Win win{0, 0};
 
   EXMC_PROF_DECL
+  EXMC_SUBPROF_DECL
   for (int draw = 0; draw < n_draws; draw++) {
     EXMC_PROF(8)
+#if EXMC_PROFILE_SECTIONS == 2
+    sub_[6] += 1;   // wave-transitions
+#endif
     // ---- transition start (sampler.ex:393-403, 890-899) ----
     bool alive = has;
     bool have_z = false;
@@ -1778,15 +1826,29 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
           // one stepping loop for both of its uses: a call's first momentum (no window yet) and the
           // groups that ran past the window
           int left = 0;
+#if EXMC_PROFILE_SECTIONS == 2
+          if (draw > 0) {
+            long long lw[2] = {0, 0};
+            draw_momentum_window<M, G>(L, win, st.rng, z_pre, left, lw);
+            EXMC_SUBPROF(0)
+            sub_[0] -= lw[0];
+            sub_[1] += lw[0];
+            sub_[5] += lw[1];
+          }
+#else
           if (draw > 0) draw_momentum_window<M, G>(L, win, st.rng, z_pre, left);
+#endif
           if (draw == 0 || __any((left < M::D) ? 1 : 0) != 0)
             draw_momentum_lean_from<M, G>(L, st.rng, z_pre, left, draw == 0);
+          EXMC_SUBPROF(2)
           momentum_from_variates<M, G>(L, z_pre, pL);
+          EXMC_SUBPROF(3)
         }
       } else {
         draw_momentum<M, G>(L, st.rng, pL);
       }
       jlp0 = st.logp - mass_ke<M, G>(L, pL);
+      EXMC_SUBPROF(4)
       trng = st.rng;  // the tree consumes a copy (sampler.ex:897 discards its draws)
 #pragma unroll
       for (int k = 0; k < DPL; k++) {
@@ -2184,6 +2246,9 @@ __device__ __forceinline__ void nuts_run(const typename M::Consts& mc, const Nut
     EXMC_PROF(6)
   }
   EXMC_PROF_FLUSH
+#if EXMC_PROFILE_SECTIONS == 2
+  EXMC_SUBPROF_FLUSH
+#endif
 }
 
 // this lane's row of cov and (negated, below the diagonal) column of chol, both row-major [D][D]
@@ -2377,41 +2442,91 @@ __global__ void __launch_bounds__(kPipe ? 2 * kNutsBlock : kNutsBlock, M::kNutsW
   const bool own = (l == 0);
   Cursor c_draw[DPL];
   Cursor c_logp, c_depth, c_steps, c_div, c_acc, c_energy;
+  // M::kPackedTrace: a group with one dimension a lane and six lanes to spare writes a trace row in two
+  // stores. Lanes 0 .. D-1 own the draw's doubles; lanes D, D+1, D+2 take accept_prob, logp and energy
+  // into the same 8-byte store, lanes D+3, D+4, D+5 tree_depth, n_steps and divergent into one 4-byte
+  // store (every lane of a group holds the six statistics already). Two cursors then, each a per-lane
+  // pointer with a per-lane step; a lane without an output, or whose output the caller left null, is
+  // switched off by the store's predicate and writes nowhere.
+  constexpr bool kPacked = M::kPackedTrace && (EXMC_FIXED_PART_PIECES & 1) != 0;
+  static_assert(!M::kPackedTrace || (DPL == 1 && G - D >= 6), "six spare lanes behind one dimension a lane");
+  Cursor c8{nullptr, 0}, c4{nullptr, 0};
+  int on_bits = 0;   // 1: this lane's 8-byte store is on, 2: its 4-byte store
   // point the cursors at trace row `row` of chain `ch`
   auto bind = [&](int ch, size_t row) {
     const size_t stat0 = row * C + ch;
+    if constexpr (kPacked) {
+      void* const b8 = (l < D) ? (void*)P.tr.draws
+                     : (l == D) ? (void*)P.tr.accept_prob
+                     : (l == D + 1) ? (void*)P.tr.logp
+                     : (l == D + 2) ? (void*)P.tr.energy : nullptr;
+      void* const b4 = (l == D + 3) ? (void*)P.tr.tree_depth
+                     : (l == D + 4) ? (void*)P.tr.n_steps
+                     : (l == D + 5) ? (void*)P.tr.divergent : nullptr;
+      on_bits = (b8 != nullptr ? 1 : 0) | (b4 != nullptr ? 2 : 0);
+      c8 = cursor(b8, true, 8, (l < D) ? (row * D + l) * C + ch : stat0, (l < D) ? (size_t)D * C : (size_t)C);
+      c4 = cursor(b4, true, 4, stat0, C);
+    } else {
 #pragma unroll
-    for (int k = 0; k < DPL; k++)
-      c_draw[k] = cursor(P.tr.draws, L.valid[k], 8, (row * D + (l + k * G)) * C + ch, (size_t)D * C);
-    c_logp = cursor(P.tr.logp, own, 8, stat0, C);
-    c_depth = cursor(P.tr.tree_depth, own, 4, stat0, C);
-    c_steps = cursor(P.tr.n_steps, own, 4, stat0, C);
-    c_div = cursor(P.tr.divergent, own, 4, stat0, C);
-    c_acc = cursor(P.tr.accept_prob, own, 8, stat0, C);
-    c_energy = cursor(P.tr.energy, own, 8, stat0, C);
+      for (int k = 0; k < DPL; k++)
+        c_draw[k] = cursor(P.tr.draws, L.valid[k], 8, (row * D + (l + k * G)) * C + ch, (size_t)D * C);
+      c_logp = cursor(P.tr.logp, own, 8, stat0, C);
+      c_depth = cursor(P.tr.tree_depth, own, 4, stat0, C);
+      c_steps = cursor(P.tr.n_steps, own, 4, stat0, C);
+      c_div = cursor(P.tr.divergent, own, 4, stat0, C);
+      c_acc = cursor(P.tr.accept_prob, own, 8, stat0, C);
+      c_energy = cursor(P.tr.energy, own, 8, stat0, C);
+    }
   };
   bind(chain, (size_t)P.draw_offset);
+  EXMC_SUBPROF_DECL
   auto sink = [&](int, const double (&sq)[DPL], double slogp, int depth, int t_n, bool t_div,
                   double t_acc, double jlp0) {
+    EXMC_SINKPROF_T0
+    if constexpr (kPacked) {
+      // every lane computes every statistic (they are uniform in the group) and then selects its own.
+      // The empty asm keeps the quotient out of a branch taken by lane D alone, and the lane predicates
+      // as compares of this call: hoisted, they are scalar register pairs spilled for the whole kernel,
+      // two v_readlane a piece at every draw
+      double acc = (t_n > 0) ? (t_acc / (double)t_n) : 0.0, energy = -jlp0;
+      int32_t dv = t_div ? 1 : 0;
+      int lr = l, on = on_bits;
+      __asm__ volatile("" : "+v"(acc), "+v"(energy), "+v"(dv), "+v"(lr), "+v"(on));
+      const double s8 = (lr == D) ? acc : ((lr == D + 1) ? slogp : energy);
+      const double v8 = (lr < D) ? sq[0] : s8;
+      const int32_t s4 = (lr == D + 3) ? depth : dv;
+      const int32_t v4 = (lr == D + 4) ? t_n : s4;
+      if ((on & 1) != 0) *(double*)c8.p = v8;
+      EXMC_SINKPROF(0)
+      if ((on & 2) != 0) *(int32_t*)c4.p = v4;
+      EXMC_SINKPROF(1)
+      c8.p += c8.step;
+      c4.p += c4.step;
+      EXMC_SINKPROF(2)
+    } else {
 #pragma unroll
-    for (int k = 0; k < DPL; k++) {
-      if (L.valid[k]) *(double*)c_draw[k].p = sq[k];
-      c_draw[k].p += c_draw[k].step;
+      for (int k = 0; k < DPL; k++) {
+        if (L.valid[k]) *(double*)c_draw[k].p = sq[k];
+        c_draw[k].p += c_draw[k].step;
+      }
+      EXMC_SINKPROF(0)
+      if (own) {
+        *(double*)c_logp.p = slogp;
+        *(int32_t*)c_depth.p = depth;
+        *(int32_t*)c_steps.p = t_n;
+        *(int32_t*)c_div.p = t_div ? 1 : 0;
+        *(double*)c_acc.p = (t_n > 0) ? (t_acc / (double)t_n) : 0.0;
+        *(double*)c_energy.p = -jlp0;
+      }
+      EXMC_SINKPROF(1)
+      c_logp.p += c_logp.step;
+      c_depth.p += c_depth.step;
+      c_steps.p += c_steps.step;
+      c_div.p += c_div.step;
+      c_acc.p += c_acc.step;
+      c_energy.p += c_energy.step;
+      EXMC_SINKPROF(2)
     }
-    if (own) {
-      *(double*)c_logp.p = slogp;
-      *(int32_t*)c_depth.p = depth;
-      *(int32_t*)c_steps.p = t_n;
-      *(int32_t*)c_div.p = t_div ? 1 : 0;
-      *(double*)c_acc.p = (t_n > 0) ? (t_acc / (double)t_n) : 0.0;
-      *(double*)c_energy.p = -jlp0;
-    }
-    c_logp.p += c_logp.step;
-    c_depth.p += c_depth.step;
-    c_steps.p += c_steps.step;
-    c_div.p += c_div.step;
-    c_acc.p += c_acc.step;
-    c_energy.p += c_energy.step;
     lf_total += (unsigned long long)t_n;
     div_total += t_div ? 1u : 0u;
     if constexpr (kStream) {
@@ -2603,6 +2718,9 @@ __global__ void __launch_bounds__(kPipe ? 2 * kNutsBlock : kNutsBlock, M::kNutsW
   }
 #ifdef EXMC_XCC_PROBE   // development: per-wave clocks, wall-clock span and placement of the sampling kernel
   probe_out();
+#endif
+#if EXMC_PROFILE_SECTIONS == 3
+  EXMC_SUBPROF_FLUSH
 #endif
 
   if (!has_chain) return;
