@@ -64,6 +64,27 @@ def test_gamma_has_the_mean_on_both_sides_of_the_boost():
         assert (g.n["boost"] == N_MOMENTS) == (alpha < 1.0)
 
 
+def test_student_t_replicates_have_the_variance():
+    """a wrong rate in the chi-square, or a wrong df under the root, changes the scale and leaves the mean"""
+    g = PS.Gen(seed=13)
+    df, loc, scale = 10.0, 0.5, 1.5
+    v = [PS.sample_student_t(df, loc, scale, g) for _ in range(N_MOMENTS)]
+    _, var = _moments(v)
+    want = scale ** 2 * df / (df - 2.0)
+    # Var(s^2) ~ sigma^4 (2 + excess kurtosis) / n, the t's excess kurtosis 6 / (df - 4)
+    assert abs(var - want) <= 5 * want * math.sqrt((2.0 + 6.0 / (df - 4.0)) / N_MOMENTS)
+
+
+def test_gamma_has_the_variance_on_both_sides_of_the_boost():
+    for alpha, seed in ((0.4, 14), (3.0, 15)):
+        g = PS.Gen(seed=seed)
+        v = [PS.sample_gamma(alpha, 0.5, g) for _ in range(N_MOMENTS)]
+        _, var = _moments(v)
+        want = alpha / 0.25
+        # the gamma's excess kurtosis is 6 / alpha
+        assert abs(var - want) <= 5 * want * math.sqrt((2.0 + 6.0 / alpha) / N_MOMENTS), alpha
+
+
 def test_the_cap_ends_a_loop_that_never_accepts():
     g = PS.Gen(seed=16)
     before = g.state()
