@@ -113,8 +113,25 @@ constexpr int kDppXor2 = 0x4E;        // quad_perm [2,3,0,1]
 constexpr int kDppHalfMirror = 0x141; // lane i <- lane 7-i within 8
 constexpr int kDppRowMirror = 0x140;  // lane i <- lane 15-i within 16
 
+// Timing only ("Round 13"): the two pieces of that round, each of which builds
+// alone for its counter run. 1: a row broadcast of a double as one 64-bit DPP move (dpp_move below);
+// 2: the seven model logarithms of tree_prefix's unit as one lane-batched evaluation (exmc_nuts.hpp
+// tree_prefix, M::kPrefixLogBatch); 4 without 2: the second piece's staging form, the model's two
+// entry points back to back in every leapfrog (more work than either: to locate a failure, not to
+// run). Same bits with any set.
+#ifndef EXMC_PREFIX_FINISH_PIECES
+#define EXMC_PREFIX_FINISH_PIECES 3
+#endif
+
+// row_newbcast:N (0x150 + N) is the one control the 64-bit DPP move of gfx950 takes: one
+// v_mov_b64_dpp for the double; every other control moves the two halves
 template <int CTRL>
 __device__ __forceinline__ double dpp_move(double v) {
+  if constexpr (CTRL >= 0x150 && CTRL <= 0x15F && (EXMC_PREFIX_FINISH_PIECES & 1) != 0) {
+    long long b = __double_as_longlong(v);
+    b = __builtin_amdgcn_update_dpp(b, b, CTRL, 0xF, 0xF, true);
+    return __longlong_as_double(b);
+  }
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
   hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
@@ -450,6 +467,18 @@ __device__ __forceinline__ void row_seqsum_lanes(double& a0, double& a1, double&
   const double one = seq_one();
   EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ3R, [a0] "+v"(a0) EXMC_COMMA [a1] "+v"(a1) EXMC_COMMA [a2] "+v"(a2),
                   [v0] "v"(v0) EXMC_COMMA [v1] "v"(v1) EXMC_COMMA [v2] "v"(v2) EXMC_COMMA [one] "v"(one) EXMC_COMMA
+                  EXMC_LANE_R(0) EXMC_COMMA EXMC_LANE_R(1) EXMC_COMMA EXMC_LANE_R(2) EXMC_COMMA EXMC_LANE_R(3) EXMC_COMMA
+                  EXMC_LANE_R(4) EXMC_COMMA EXMC_LANE_R(5) EXMC_COMMA EXMC_LANE_R(6) EXMC_COMMA EXMC_LANE_R(7) EXMC_COMMA
+                  EXMC_LANE_R(8) EXMC_COMMA EXMC_LANE_R(9) EXMC_COMMA EXMC_LANE_R(10) EXMC_COMMA EXMC_LANE_R(11))
+}
+// ... one sum (EightSchools::logp_finish: the chain behind its first step, lanes 1 .. 9)
+#define EXMC_SEQ1R(I) EXMC_FMAC_R(a0, v0, I)
+template <int I0, int NL>
+__device__ __forceinline__ void row_seqsum_lanes(double& a0, double v0) {
+  static_assert(I0 >= 0 && NL >= 1 && NL <= 12 && I0 + NL <= 16, "a lane range of one DPP row");
+  const double one = seq_one();
+  EXMC_SEQSUM_ASM_H(EXMC_NOP2, EXMC_SEQ1R, [a0] "+v"(a0),
+                  [v0] "v"(v0) EXMC_COMMA [one] "v"(one) EXMC_COMMA
                   EXMC_LANE_R(0) EXMC_COMMA EXMC_LANE_R(1) EXMC_COMMA EXMC_LANE_R(2) EXMC_COMMA EXMC_LANE_R(3) EXMC_COMMA
                   EXMC_LANE_R(4) EXMC_COMMA EXMC_LANE_R(5) EXMC_COMMA EXMC_LANE_R(6) EXMC_COMMA EXMC_LANE_R(7) EXMC_COMMA
                   EXMC_LANE_R(8) EXMC_COMMA EXMC_LANE_R(9) EXMC_COMMA EXMC_LANE_R(10) EXMC_COMMA EXMC_LANE_R(11))

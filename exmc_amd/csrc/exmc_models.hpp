@@ -110,6 +110,11 @@ struct ModelDefaults {
   // one, the three 4-byte statistics in the other, each statistic from a spare lane of the group
   // (exmc_nuts.hpp nuts_kernel). Needs one dimension a lane and six lanes of the group past D.
   static constexpr bool kPackedTrace = false;
+  // With kTreePrefix: the model's value in two steps, logp_grad_pre (the gradient and, one double a
+  // lane, what the value still lacks: the argument of one logarithm among it) and logp_finish (the
+  // value from that and the logarithm). tree_prefix then evaluates the logarithms of its seven leaves
+  // as one lane-batched log_ge1 after the seventh leapfrog; same function on the same bits.
+  static constexpr bool kPrefixLogBatch = false;
 };
 
 // the dynamic LDS of the running kernel (every extern __shared__ array names the same base)
@@ -282,6 +287,37 @@ struct EightSchools : ModelDefaults {
     Mid m;
     eval_row_grad(c, ln, l, q, g, dv, m);
     return eval_row_finish(c, l, m, MM::log_ge1(m.den));
+  }
+
+  // The row form's value in two calls (ModelDefaults::kPrefixLogBatch). logp_grad_pre is the gradient
+  // phase, exact-division replay included, and returns per lane what the value still lacks: lane 0
+  // lik + T_0 -- the first step of the finish's chain, fma(T_0, 1, lik), as the plain add it is --,
+  // lanes 2 .. 9 their T, and lane 1 and every lane past the dimensions den = 1 + zt^2, the argument
+  // of the half-Cauchy term's logarithm (those lanes run lane 1's instruction stream on tau). So the
+  // arguments of up to seven evaluations sit on seven different lanes without a move: evaluation k
+  // on lane pre_log_lane(k). logp_finish takes lg = log_ge1(den) and q, forms lane 1's term with
+  // zc = clamp200 of its own q and runs the rest of the chain, lanes 1 .. 9; it divides nothing.
+  static constexpr bool kPrefixLogBatch = (G == 16);
+  static constexpr int kPreLogLanes = (G == 16) ? 1 + (G - D) : 0;
+  __device__ static constexpr int pre_log_lane(int k) { return k == 0 ? 1 : D + k - 1; }
+  __device__ static __forceinline__ double logp_grad_pre(const Consts& c, const Lane& ln, int l,
+                                                         const double (&q)[DPL], double (&g)[DPL]) {
+    static_assert(kSeqSum<G, D>, "the row form");
+    return with_fast_div([&](auto& dv) -> double {
+      Mid m;
+      eval_row_grad(c, ln, l, q, g, dv, m);
+      const double head = m.lik + m.T;
+      return (l == 0) ? head : (((l >= 2) && (l < D)) ? m.T : m.den);
+    });
+  }
+  __device__ static __forceinline__ double logp_finish(const Consts& c, int l, const double (&q)[DPL],
+                                                       double pre, double lg) {
+    double t_tau = (c.c_hc - lg) + clamp200(q[0]);
+    __asm__("" : "+v"(t_tau));
+    const double T = (l == 1) ? t_tau : pre;
+    double acc = group_bcast_c<G, 0>(pre);
+    row_seqsum_lanes<1, D - 1>(acc, T);
+    return acc;
   }
 
   template <class DV>
@@ -1732,6 +1768,7 @@ struct RowDenseModel : M {
   static constexpr bool kOuterLogPair = false;
   static constexpr bool kTreePrefix = false;   // likewise (exmc_nuts.hpp tree_prefix)
   static constexpr bool kRngWindow = false;    // (the window is built inside tree_prefix)
+  static constexpr bool kPrefixLogBatch = false;   // (the unit's model logarithms as one: inside tree_prefix)
   static constexpr bool kPackedTrace = false;  // (the trace row in two stores: the diagonal-mass kernels only)
   static_assert(M::DPL == 1 && M::D <= 12, "row layout: one dimension per lane, D <= 12");
 };

@@ -1443,6 +1443,8 @@ struct TreeTop {
 //   4 log  the level-1 merge's and doubling 1's outer log_ge1
 //   5 exp  the level-1 merge's proposal weight, doubling 2's outer log_sum_exp
 //   6 log  doubling 2's outer log_ge1
+// and, where the model splits its value (M::kPrefixLogBatch), in front of the scalars
+//   0 log  the one logarithm each of the seven model values still lacks
 // Each value comes from the function that computes it in the walk (exp_le0, lse_arg / lse_finish,
 // log_main with its fix-ups), the merges run in the walk's order -- pair units, the level-1 merge,
 // the three outer merges -- and take their uniforms in the walk's order: u[0] direction, u[1] outer
@@ -1496,13 +1498,25 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   const bool r0 = U(IntC<0>{}) > 0.5, r1 = U(IntC<2>{}) > 0.5, r2 = U(IntC<5>{}) > 0.5;   // tree.ex:403
 
   // ---- the seven leapfrogs (batched_leapfrog.ex:79-85), as leaf_pair integrates them ----
+  // M::kPrefixLogBatch: a leapfrog leaves in lf.logp what logp_grad_pre returns -- one double a lane,
+  // like the value it stands for -- and the values are finished behind the seventh leapfrog, the seven
+  // logarithms they lack as one evaluation (a leaf's value is read by the scalars first, its argument
+  // never feeds a gradient). EXMC_PREFIX_FINISH_PIECES 4 without 2: the same two calls back to back.
+  constexpr bool kSplitLogp = M::kPrefixLogBatch && (EXMC_PREFIX_FINISH_PIECES & 6) != 0;
+  constexpr bool kLogBatch = kSplitLogp && (EXMC_PREFIX_FINISH_PIECES & 2) != 0;
   PipeLeaf<DPL> f0, f1, f2, f3, f4, f5, f6;
   auto leap = [&](double eps_dir, PipeLeaf<DPL>& lf) {
     const double h = eps_dir / 2.0;
 #pragma unroll
     for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
     mass_drift<M, G>(L, eps_dir, p, q);
-    lf.logp = M::logp_grad(mc, L.ln, L.l, q, g);
+    if constexpr (kSplitLogp) {
+      lf.logp = M::logp_grad_pre(mc, L.ln, L.l, q, g);
+      if constexpr (!kLogBatch)
+        lf.logp = M::logp_finish(mc, L.l, q, lf.logp, MM::log_ge1(group_bcast_c<G, M::pre_log_lane(0)>(lf.logp)));
+    } else {
+      lf.logp = M::logp_grad(mc, L.ln, L.l, q, g);
+    }
 #pragma unroll
     for (int k = 0; k < DPL; k++) p[k] = p[k] + h * g[k];
 #pragma unroll
@@ -1533,6 +1547,27 @@ __device__ __forceinline__ void tree_prefix(const typename M::Consts& mc, const 
   leap(r2 ? eps : -eps, f4);
   leap(r2 ? eps : -eps, f5);
   leap(r2 ? eps : -eps, f6);
+
+  // ---- the seven values finished: leaf k's argument stands on lane pre_log_lane(k) of its record
+  // already, so the gather is six selects; one log_ge1 -- the model's own, with its fix-up, on
+  // whatever the other lanes hold (straight-line arithmetic) --, a broadcast back per leaf ----
+  if constexpr (kLogBatch) {
+    static_assert(M::kPreLogLanes >= 7, "a lane per leaf of the unit");
+    const int l = L.l;
+    double a = f0.logp;
+    a = (l == M::pre_log_lane(1)) ? f1.logp : a;
+    a = (l == M::pre_log_lane(2)) ? f2.logp : a;
+    a = (l == M::pre_log_lane(3)) ? f3.logp : a;
+    a = (l == M::pre_log_lane(4)) ? f4.logp : a;
+    a = (l == M::pre_log_lane(5)) ? f5.logp : a;
+    a = (l == M::pre_log_lane(6)) ? f6.logp : a;
+    const double v = MM::log_ge1(a);
+    auto finish = [&](PipeLeaf<DPL>& lf, auto ic) {
+      lf.logp = M::logp_finish(mc, l, lf.q, lf.logp, group_bcast_c<G, M::pre_log_lane(decltype(ic)::value)>(v));
+    };
+    finish(f0, IntC<0>{}); finish(f1, IntC<1>{}); finish(f2, IntC<2>{}); finish(f3, IntC<3>{});
+    finish(f4, IntC<4>{}); finish(f5, IntC<5>{}); finish(f6, IntC<6>{});
+  }
 
   // ---- the leaves' scalars (tree.ex:1042-1048 without a branch, see leaf_pair) and batch 1 ----
   auto scalars = [&](PipeLeaf<DPL>& lf) -> double {
