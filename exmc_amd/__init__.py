@@ -2,7 +2,7 @@
 
 Package layout: csrc/ (HIP kernels + the C ABI of libexmc_hip.so), sampler.py (host mirror of
 Exmc.NUTS.Sampler), pathfinder.py (host mirror of Exmc.Pathfinder), advi.py (host mirror of Exmc.ADVI),
-predictive.py (host mirror of Exmc.Predictive.posterior_predictive),
+predictive.py (host mirror of Exmc.Predictive: prior_samples and posterior_predictive),
 models.py (model kinds of the BASELINE configs), build.py (hipcc driver).
 If torch is going to be used in the same process it must load its HIP runtime first, so it is
 imported here before libexmc_hip.so whenever it is installed.

@@ -51,6 +51,9 @@ ADVI_EXPORTS = ["exmc_hip_advi", "exmc_hip_advi_host"]
 # include/exmc_hip_predictive.h: Exmc.Predictive.posterior_predictive, one chain's generator per lane
 PREDICTIVE_EXPORTS = ["exmc_hip_posterior_predictive", "exmc_hip_posterior_predictive_host"]
 
+# include/exmc_hip_prior.h: Exmc.Predictive.prior_samples, the prior walk and the datums' replicates per lane
+PRIOR_EXPORTS = ["exmc_hip_prior_samples", "exmc_hip_prior_samples_host"]
+
 # include/exmc_hip_ppc.h: posterior predictive checks, the replicates reduced where they are drawn
 PPC_EXPORTS = ["exmc_hip_ppc", "exmc_hip_ppc_host"]
 PPC_BLOCK = 64
@@ -199,6 +202,8 @@ def bind(path):
     L.exmc_hip_advi_host.argtypes = [vp, AdviOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
     L.exmc_hip_posterior_predictive.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.exmc_hip_posterior_predictive_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, up, dp]
+    L.exmc_hip_prior_samples.argtypes = [vp, PredictiveOpts, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.exmc_hip_prior_samples_host.argtypes = [vp, PredictiveOpts, C.c_int, C.c_int, up, dp, dp, dp]
     L.exmc_hip_ppc.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, dp, dp, dp]
     L.exmc_hip_ppc_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp]
     L.exmc_hip_loo_pit.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]

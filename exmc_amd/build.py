@@ -33,6 +33,7 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_predictive.hpp"),
     os.path.join(HERE, "csrc", "exmc_ppc.hpp"),
     os.path.join(HERE, "csrc", "exmc_loo_pit.hpp"),
+    os.path.join(HERE, "csrc", "exmc_prior.hpp"),
     os.path.join(HERE, "csrc", "exmc_plugin_part.hip"),
     COMMON_SRC,
     os.path.join(HERE, "csrc", "exmc_plugin_kernels.inc"),
@@ -46,6 +47,7 @@ DEPS = [
     os.path.join(ROOT, "include", "exmc_hip_predictive.h"),
     os.path.join(ROOT, "include", "exmc_hip_ppc.h"),
     os.path.join(ROOT, "include", "exmc_hip_loo_pit.h"),
+    os.path.join(ROOT, "include", "exmc_hip_prior.h"),
     os.path.join(ROOT, "include", "exmc_hip_convergence.h"),
     os.path.join(ROOT, "include", "exmc_detmath.h"),
     os.path.join(ROOT, "include", "exmc_logtab.h"),

@@ -2638,6 +2638,85 @@ void pp_fill(Params& P, exmc_hip_model* m, const exmc_hip_predictive_opts& o, co
   P.rng = rng_args(m);
 }
 
+#ifndef EXMC_ONLY_CUSTOM
+// ---- the prior walk (include/exmc_hip_prior.h; prior_kernel, exmc_prior.hpp) --------------------------
+// The free variables of the kind, indexed by kernel dimension, as the IR the kind stands for has them
+// after Rewrite.apply: the family, the transform and the two parameters, a literal (ref < 0) or the
+// kernel dimension of the parent. The literals are those of the kind's log-density (exmc_models.hpp).
+std::vector<PriorEntry> prior_vars(const exmc_hip_model* m) {
+  std::vector<PriorEntry> v((size_t)m->d);
+  auto set = [&](int j, int family, int log, double a, double b, int ra = -1, int rb = -1) {
+    v[j] = PriorEntry{j, family, log, {ra, rb}, 0, {a, b}};
+  };
+  switch (m->kind) {
+    case EXMC_MODEL_SIMPLE:
+      set(0, kPriorNormal, 0, 0.0, 5.0);
+      set(1, kPriorExponential, 1, 1.0, 0.0);
+      break;
+    case EXMC_MODEL_EIGHT_SCHOOLS:
+      set(0, kPriorNormal, 0, 0.0, 5.0);
+      set(1, kPriorHalfCauchy, 1, 5.0, 0.0);
+      for (int j = 2; j < 10; j++) set(j, kPriorNormal, 0, 0.0, 1.0);
+      break;
+    case EXMC_MODEL_SV:
+    case EXMC_MODEL_SV_NCP:
+      // s_1 ~ N(0.0, sigma); s_t ~ N(s_{t-1}, sigma), which the non-centring pass rewrites to z_t ~ N(0, 1)
+      set(0, kPriorNormal, 0, 0.0, 0.0, -1, 100);
+      for (int t = 1; t < 100; t++) {
+        if (m->kind == EXMC_MODEL_SV_NCP) set(t, kPriorNormal, 0, 0.0, 1.0);
+        else set(t, kPriorNormal, 0, 0.0, 0.0, t - 1, 100);
+      }
+      set(100, kPriorExponential, 1, m->sv.lam_s, 0.0);
+      set(101, kPriorExponential, 1, m->sv.lam_n, 0.0);
+      break;
+    case EXMC_MODEL_LOGISTIC:
+      for (int j = 0; j < m->d; j++) set(j, kPriorNormal, 0, 0.0, 10.0);
+      break;
+    case EXMC_MODEL_RADON:
+      for (int j = 0; j < 85; j++) set(j, kPriorNormal, 0, 0.0, 1.0);
+      set(85, kPriorNormal, 0, 0.0, 10.0);        // mu_alpha
+      set(86, kPriorNormal, 0, 0.0, 5.0);         // gamma_u
+      set(87, kPriorHalfCauchy, 1, 2.5, 0.0);     // sigma_alpha
+      set(88, kPriorHalfCauchy, 1, 2.5, 0.0);     // sigma_y
+      set(89, kPriorNormal, 0, 0.0, 5.0);         // beta
+      break;
+    default: v.clear();
+  }
+  return v;
+}
+
+// kahn_sort (predictive.ex:159-196): always the smallest ready id by string comparison, the string
+// order being the handle's flat order
+std::vector<PriorEntry> prior_program(const exmc_hip_model* m) {
+  const std::vector<PriorEntry> v = prior_vars(m);
+  const int d = (int)v.size();
+  std::vector<int> deg((size_t)d, 0);
+  std::vector<char> done((size_t)d, 0);
+  for (int j = 0; j < d; j++) deg[j] = (v[j].ref[0] >= 0) + (v[j].ref[1] >= 0);
+  auto rank = [&](int j) { return m->h_rank.empty() ? j : (int)m->h_rank[j]; };
+  std::vector<PriorEntry> prog;
+  for (int n = 0; n < d; n++) {
+    int pick = -1;
+    for (int j = 0; j < d; j++)
+      if (!done[j] && deg[j] == 0 && (pick < 0 || rank(j) < rank(pick))) pick = j;
+    if (pick < 0) break;   // (no built-in kind has a cycle)
+    done[pick] = 1;
+    prog.push_back(v[pick]);
+    for (int j = 0; j < d; j++)
+      if (!done[j] && (v[j].ref[0] == pick || v[j].ref[1] == pick)) deg[j]--;
+  }
+  return prog;
+}
+
+#endif
+
+// what exmc_hip_prior_samples and its _host form ask of their arguments (pp_check; x stands where the
+// trace stands there)
+int prior_check(exmc_hip_model* m, const exmc_hip_predictive_opts& o, int n_draws, int n_chains, const void* x,
+                const void* q, const void* rng_state) {
+  return pp_check(m, "prior samples", o, x, n_draws, m ? m->d : 0, n_chains, !q || (o.resume && !rng_state));
+}
+
 }  // namespace
 
 extern "C" {
@@ -2801,6 +2880,72 @@ int exmc_hip_posterior_predictive_host(exmc_hip_model* m, exmc_hip_predictive_op
   if (!rc) rc = sc.download();
   if (rc) return rc;
   transpose_trace_vec(sc.host(s_yrep), yrep, n_draws, (int)N, n_chains);
+  if (rng_state) std::copy(sc.host(s_rng), sc.host(s_rng) + 2 * C, rng_state);
+#endif
+  return rc;
+}
+
+// ---- prior and prior predictive samples (include/exmc_hip_prior.h; prior_kernel, exmc_prior.hpp) -------
+int exmc_hip_prior_samples(exmc_hip_model* m, exmc_hip_predictive_opts o, int n_draws, int n_chains,
+                           uint64_t* rng_state_dev, double* x_dev, double* q_dev, double* yrep_dev) {
+  int rc = prior_check(m, o, n_draws, n_chains, x_dev, q_dev, rng_state_dev);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)yrep_dev;
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const std::vector<PriorEntry> prog = prior_program(m);
+  if ((int)prog.size() != m->d) return fail(EXMC_ERR_UNSUPPORTED, "prior samples: this model kind has no prior walk");
+  CallBuf dprog;
+  rc = dprog.alloc(prog.size() * sizeof(PriorEntry));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(dprog.p, prog.data(), prog.size() * sizeof(PriorEntry), hipMemcpyHostToDevice));
+  PriorParams P;
+  P.prog = dprog.as<PriorEntry>();
+  P.x = x_dev;
+  P.q = q_dev;
+  P.yrep = yrep_dev;
+  P.rng_state = rng_state_dev;
+  P.S = n_draws;
+  P.d = m->d;
+  P.C = n_chains;
+  P.N = ic_n_data(m);
+  P.chain_lo = o.chain_lo;
+  P.resume = o.resume ? 1 : 0;
+  P.xwalk = (m->kind == EXMC_MODEL_SV_NCP) ? 100 : 0;
+  P.base_seed = o.seed;
+  P.rng = rng_args(m);
+  rc = ic_with_src(m, [&](const auto& src) {
+    using Src = std::decay_t<decltype(src)>;
+    return pp_launch(m, prior_kernel<Src>, pp_lds_bytes(m->d), src, P);   // waits: before the program is freed
+  });
+#endif
+  return rc;
+}
+
+int exmc_hip_prior_samples_host(exmc_hip_model* m, exmc_hip_predictive_opts o, int n_draws, int n_chains,
+                                uint64_t* rng_state, double* x, double* q, double* yrep) {
+  int rc = prior_check(m, o, n_draws, n_chains, x, q, rng_state);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)yrep;
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t S = (size_t)n_draws, C = (size_t)n_chains, d = (size_t)m->d, N = (size_t)ic_n_data(m);
+  Scratch sc;
+  const auto s_x = sc.take<double>(S * d * C), s_q = sc.take<double>(S * d * C);   // [S][d][C]
+  const auto s_yrep = sc.take<double>(yrep ? S * N * C : 0);                       // [S][N][C]
+  const auto s_rng = sc.take<uint64_t>(rng_state ? 2 * C : 0);                     // the generators [2][C]
+  rc = sc.alloc();
+  if (rc) return rc;
+  if (rng_state && o.resume) HIP_TRY(hipMemcpy(sc.dev(s_rng), rng_state, 2 * C * 8, hipMemcpyHostToDevice));
+  rc = exmc_hip_prior_samples(m, o, n_draws, n_chains, rng_state ? sc.dev(s_rng) : nullptr, sc.dev(s_x), sc.dev(s_q),
+                              yrep ? sc.dev(s_yrep) : nullptr);
+  if (!rc) rc = sc.download();
+  if (rc) return rc;
+  transpose_trace_vec(sc.host(s_x), x, n_draws, (int)d, n_chains);
+  transpose_trace_vec(sc.host(s_q), q, n_draws, (int)d, n_chains);
+  if (yrep) transpose_trace_vec(sc.host(s_yrep), yrep, n_draws, (int)N, n_chains);
   if (rng_state) std::copy(sc.host(s_rng), sc.host(s_rng) + 2 * C, rng_state);
 #endif
   return rc;

@@ -244,4 +244,5 @@ __global__ void __launch_bounds__(kNutsBlock) find_eps_kernel(FindEpsParams P,
 #include "exmc_predictive.hpp"      // predictive_kernel: Exmc.Predictive, one chain's generator per lane
 #include "exmc_ppc.hpp"             // ppc_kernel: posterior predictive checks, the replicates reduced in place
 #include "exmc_loo_pit.hpp"         // loo_pit_kernel: PSIS-LOO-PIT, the replicates weighted where they are drawn
+#include "exmc_prior.hpp"           // prior_kernel: Exmc.Predictive.prior_samples, every lane fills its own row
 #endif

@@ -1,6 +1,9 @@
-"""Host-side mirror of Exmc.Predictive.posterior_predictive (lib/exmc/predictive.ex:44-63) over the
-device kernel.
+"""Host-side mirror of Exmc.Predictive (lib/exmc/predictive.ex: prior_samples :19-33, posterior_predictive
+:44-63) over the device kernels.
 
+    prior_samples(compiled, n, chains, seed=0)     -> {name: [C][n] numpy, x, q, yrep device tensors, names}:
+                                                      the prior walk and the prior predictive replicates
+    prior_samples_blocks(compiled, n, chains, block_draws, seed=0) -> yields (s0, dict of the block)
     posterior_predictive(compiled, draws, seed=0)  -> (yrep [S][N][C] device tensor, datum names)
     posterior_predictive_blocks(compiled, draws, block_draws, seed=0) -> yields (s0, yrep block)
     as_trace(yrep, names)                          -> {name: [C][S] numpy}, the reference's map
@@ -89,6 +92,75 @@ def as_trace(yrep, names):
     if a.ndim != 3 or a.shape[1] != len(names):
         raise ValueError("yrep must be [S][N][C] with one name per datum")
     return {name: np.ascontiguousarray(a[:, i, :].T) for i, name in enumerate(names)}
+
+
+# ---- prior and prior predictive samples (include/exmc_hip_prior.h, DESIGN.md "Prior predictive") ---------
+def _prior_call(compiled, n, Cn, seed, chain_lo, resume, state, x, q, yrep):
+    opts = _lib.PredictiveOpts(int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_lo), 1 if resume else 0)
+    compiled.check(compiled.L.exmc_hip_prior_samples(
+        compiled.h, opts, int(n), int(Cn), None if state is None else state.data_ptr(), x.data_ptr(), q.data_ptr(),
+        None if yrep is None else yrep.data_ptr()))
+
+
+def _prior_result(compiled, x, q, yrep, N):
+    xs = x.cpu().numpy()
+    out = {name: np.ascontiguousarray(xs[:, j, :].T) for j, name in enumerate(compiled.spec.var_names)}
+    out.update(x=x, q=q, yrep=yrep, names=_names(compiled, N) if yrep is not None else [])
+    return out
+
+
+def _prior_bytes(n, d, N, Cn, replicates):
+    return n * (2 * d + (N if replicates else 0)) * Cn * 8
+
+
+def prior_samples(compiled, n, chains, seed=0, chain_lo=0, replicates=True, max_bytes=PREDICTIVE_MAX_BYTES):
+    """Exmc.Predictive.prior_samples (lib/exmc/predictive.ex:19-33) of a built-in kind: n draws of every free
+    variable from its prior in each of `chains` chains, chain c with one generator seeded with seed + 7919
+    (chain_lo + c), the variables of a draw in the reference's Kahn order, and with replicates=True the
+    prior predictive replicates of every datum after them. A dict: per variable name a numpy [C][n] of
+    constrained values (the reference's map, per chain); `x` and `q`, the float64 device tensors [n][d][C]
+    of the constrained values and of the unconstrained position in kernel order (q is a trace for
+    posterior_predictive, ppc and the pointwise terms); `yrep`, the device tensor [n][N][C] in the handle's
+    datum order, or None; `names`, the datum names in that order. With replicates=False no datum is drawn
+    and the generators do not advance for them. Refuses results above max_bytes: prior_samples_blocks
+    yields them a block of draws at a time."""
+    import torch
+    n, Cn = int(n), int(chains)
+    N, d = n_data(compiled), compiled.d
+    if n >= 1 and Cn >= 1 and _prior_bytes(n, d, N, Cn, replicates) > max_bytes:
+        raise ValueError("the prior samples would take %.1f GB (limit %.1f GB): use prior_samples_blocks, "
+                         "which yields them a block of draws at a time"
+                         % (_prior_bytes(n, d, N, Cn, replicates) / 1e9, max_bytes / 1e9))
+    dev = torch.device("cuda", compiled.device)
+    x = torch.empty((max(n, 0), d, max(Cn, 0)), dtype=torch.float64, device=dev)
+    q = torch.empty_like(x)
+    yrep = torch.empty((max(n, 0), N, max(Cn, 0)), dtype=torch.float64, device=dev) if replicates else None
+    _ordered_after_torch(x)
+    _prior_call(compiled, n, Cn, seed, chain_lo, False, None, x, q, yrep)
+    torch.cuda.synchronize(dev)
+    return _prior_result(compiled, x, q, yrep, N)
+
+
+def prior_samples_blocks(compiled, n, chains, block_draws, seed=0, chain_lo=0, replicates=True):
+    """A generator of (s0, dict) over the n draws in blocks of block_draws, the chains' generators carried
+    from block to block on the device: the blocks joined are prior_samples' result, bit for bit. Every
+    block's dict is prior_samples' of its draws, with tensors of its own; the last may be shorter."""
+    import torch
+    if int(block_draws) < 1:
+        raise ValueError("block_draws must be >= 1")
+    n, Cn = int(n), int(chains)
+    N, d = n_data(compiled), compiled.d
+    dev = torch.device("cuda", compiled.device)
+    state = torch.zeros((2, max(Cn, 0)), dtype=torch.int64, device=dev)   # the bits of the uint64 [2][C]
+    for s0 in range(0, n, int(block_draws)):
+        ns = min(int(block_draws), n - s0)
+        x = torch.empty((ns, d, Cn), dtype=torch.float64, device=dev)
+        q = torch.empty_like(x)
+        yrep = torch.empty((ns, N, Cn), dtype=torch.float64, device=dev) if replicates else None
+        _ordered_after_torch(state)
+        _prior_call(compiled, ns, Cn, seed, chain_lo, s0 > 0, state, x, q, yrep)
+        torch.cuda.synchronize(dev)
+        yield s0, _prior_result(compiled, x, q, yrep, N)
 
 
 PPC_STATS = ("mean", "var", "min", "max")

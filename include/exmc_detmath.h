@@ -338,6 +338,60 @@ EXMC_HD double exmc_erf(double x) {
   return x < 0.0 ? -r : r;
 }
 
+/* tan((pi/2) u) for u in [0, 1], for HalfCauchy.sample (lib/exmc/dist/half_cauchy.ex:34-40 draws
+ * scale_f * abs(:math.tan(:math.pi() * u * 0.5)); libm's tan is not in the numeric contract).
+ * DEVIATION from the reference: this is the tangent of the EXACT (pi/2) u, not of the rounded product
+ * pi * u * 0.5. Near u = 1 the two differ visibly: the reference's argument sits an ulp of pi/2 away
+ * from the pole, so :math.tan never exceeds 1.7e16 and changes sign where the product rounds past
+ * pi/2; here f(u) grows as (2/pi) / (1 - u) up to f(1) = +inf and is never negative.
+ *   v = (u <= 0.5) ? u : 1 - u          exact (Sterbenz above 0.5), so v is in [0, 0.5]
+ *   v <= 0.375 : x + y = (pi/2) v as a double-double (pi/2 in two doubles, the product's residual by
+ *                fma), t = tan(x + y) by the odd degree-27 polynomial of fdlibm's __kernel_tan
+ *                (its 13 published coefficients, valid below 0.6744; x <= 0.59 here)
+ *   v >  0.375 : w = 0.5 - v (exact), t = tan((pi/2) w) as above, and tan(pi/4 - a) = (1 - t) / (1 + t)
+ *                = 1 - 2 (t - t^2 / (1 + t))
+ *   u >  0.5   : the reciprocal, 1 / f(1 - u)
+ * Only +, -, *, fma, IEEE / and comparisons; host and device give the same bits.
+ * Exactly: f(0) = +0, f(0.5) = 1, f(1) = +inf; NaN and arguments outside [0, 1] give NaN; the result
+ * is never negative. Accuracy: tests/test_detmath_tan.py against a 50-digit evaluation, DESIGN.md
+ * "Prior predictive" states the measured bound. */
+EXMC_HD double exmc_tan_halfpi_core(double v) {   /* tan((pi/2) v), 0 <= v <= 0.375 */
+  const double x = v * 1.57079632679489655800e+00;                              /* pi/2, high */
+  const double y = __builtin_fma(v, 6.12323399573676603587e-17,                 /* pi/2, low */
+                                 __builtin_fma(v, 1.57079632679489655800e+00, -x));
+  const double z = x * x;
+  const double w = z * z;
+  double r = -1.85586374855275456654e-05;                                       /* T11 .. T1, odd, in w */
+  r = __builtin_fma(w, r, 7.81794442939557092300e-05);
+  r = __builtin_fma(w, r, 5.88041240820264096874e-04);
+  r = __builtin_fma(w, r, 3.59207910759131235356e-03);
+  r = __builtin_fma(w, r, 2.18694882948595424599e-02);
+  r = __builtin_fma(w, r, 1.33333333333201242699e-01);
+  double e = 2.59073051863633712884e-05;                                        /* T12 .. T2, even, in w */
+  e = __builtin_fma(w, e, 7.14072491382608190305e-05);
+  e = __builtin_fma(w, e, 2.46463134818469906812e-04);
+  e = __builtin_fma(w, e, 1.45620945432529025516e-03);
+  e = __builtin_fma(w, e, 8.86323982359930005737e-03);
+  e = __builtin_fma(w, e, 5.39682539762260521377e-02);
+  const double s = z * x;
+  r = __builtin_fma(z, __builtin_fma(s, __builtin_fma(z, e, r), y), y);
+  r = __builtin_fma(3.33333333333334091986e-01, s, r);                          /* T0 */
+  return x + r;
+}
+
+EXMC_HD double exmc_tan_halfpi(double u) {
+  if (!(u >= 0.0 && u <= 1.0)) return exmc_from_bits(EXMC_NAN_BITS);
+  const double v = ((u <= 0.5) ? u : 1.0 - u) + 0.0;   /* + 0.0: a negative zero goes in as +0 */
+  double f;
+  if (v <= 0.375) {
+    f = exmc_tan_halfpi_core(v);
+  } else {
+    const double t = exmc_tan_halfpi_core(0.5 - v);
+    f = 1.0 - 2.0 * (t - (t * t) / (1.0 + t));
+  }
+  return (u <= 0.5) ? f : 1.0 / f;
+}
+
 /* ---- the same functions for arguments whose range the call site proves ----
  * exmc_exp / exmc_log guard every special case (NaN, overflow, underflow, zero, negative,
  * subnormal, infinity) with a branch; on the GPU each guard is a compare, an exec-mask save, a
