@@ -48,6 +48,12 @@ PF_MAX_HISTORY = 6
 # include/exmc_hip_advi.h: Exmc.ADVI, one mean-field fit per lane group
 ADVI_EXPORTS = ["exmc_hip_advi", "exmc_hip_advi_host"]
 
+# include/exmc_hip_fit_psis.h: the Pareto-smoothed importance ratios of the fits' draws and their resampling
+FIT_PSIS_EXPORTS = ["exmc_hip_fit_log_ratio", "exmc_hip_ratio_psis_from_lr", "exmc_hip_ratio_gather",
+                    "exmc_hip_fit_psis", "exmc_hip_fit_psis_host"]
+FIT_SIGMA, FIT_LOG_SIGMA = 0, 1
+FIT_PSIS_ROWS = ("khat", "log_mean_ratio", "ess", "n_zero", "tail")
+
 # include/exmc_hip_predictive.h: Exmc.Predictive.posterior_predictive, one chain's generator per lane
 PREDICTIVE_EXPORTS = ["exmc_hip_posterior_predictive", "exmc_hip_posterior_predictive_host"]
 
@@ -200,6 +206,13 @@ def bind(path):
     L.exmc_hip_pathfinder_host.argtypes = [vp, PfOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip, ip]
     L.exmc_hip_advi.argtypes = [vp, AdviOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.exmc_hip_advi_host.argtypes = [vp, AdviOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
+    L.exmc_hip_fit_log_ratio.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.exmc_hip_ratio_psis_from_lr.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp, vp]
+    L.exmc_hip_ratio_gather.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.exmc_hip_fit_psis.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_uint64, vp, vp, vp, vp, vp, vp]
+    L.exmc_hip_fit_psis_host.argtypes = [vp, dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_uint64, dp, dp, ip, dp, dp, dp]
     L.exmc_hip_posterior_predictive.argtypes = [vp, PredictiveOpts, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.exmc_hip_posterior_predictive_host.argtypes = [vp, PredictiveOpts, dp, C.c_int, C.c_int, C.c_int, up, dp]
     L.exmc_hip_prior_samples.argtypes = [vp, PredictiveOpts, C.c_int, C.c_int, vp, vp, vp, vp]

@@ -77,3 +77,15 @@ def fit(ir_or_compiled, opts=None, num_fits=1):
     if int(num_fits) == 1:
         return draws[0], infos[0]
     return draws, infos, int(np.argmax(score))
+
+
+def fit_psis(ir_or_compiled, opts=None, num_fits=1, pooled=False, num_resample=0, resample_seed=0):
+    """fit_raw, then importance.psis_fit over its fits: the Pareto k of every fit (or of the pool), the
+    smoothed log weights and, with num_resample > 0, the importance-resampled draws. Returns (raw, result)."""
+    o = _validate(opts, num_fits)
+    from . import importance, sampler
+    compiled = ir_or_compiled if isinstance(ir_or_compiled, sampler.Compiled) else \
+        sampler.Compiled(ir_or_compiled, device=o.get("device", 0))
+    raw = fit_raw(compiled, o, num_fits)
+    return raw, importance.psis_fit(compiled, raw, pooled=pooled, num_resample=num_resample, seed=resample_seed,
+                                    lanes_per_chain=int(o.get("lanes_per_chain") or 0))

@@ -11,6 +11,7 @@
 #include "../../include/exmc_hip_compare.h"
 #include "../../include/exmc_hip_pathfinder.h"
 #include "../../include/exmc_hip_advi.h"
+#include "../../include/exmc_hip_fit_psis.h"
 #include "../../include/exmc_hip_predictive.h"
 #include "../../include/exmc_hip_ppc.h"
 #include "../../include/exmc_hip_loo_pit.h"
@@ -36,6 +37,7 @@
 #include "exmc_layout_host.hpp"
 #include "exmc_ic.hpp"
 #include "exmc_psis.hpp"
+#include "exmc_psis_ratio.hpp"
 
 using namespace exmc;
 using namespace exmc::host;
@@ -2121,15 +2123,16 @@ PsisTables psis_tables(const PsisScratch& sc) {
   return {sc.keys.as<uint64_t>(), sc.idx.as<uint32_t>(), sc.xs.as<double>(), sc.meta.as<double>(), sc.M, sc.P};
 }
 
-// the tails of ll[S][Nb][C] into the tables
+// the tails of ll[S][Nb][C] into the tables (kRatio: of the log ratios lr[S][Nb][C], exmc_psis_ratio.hpp)
+template <bool kRatio = false>
 int psis_tails(hipStream_t stream, const PsisTables& t, const double* ll, int S, int Nb, int C) {
   if (t.P <= kPsisLdsPairs) {
     const size_t lds = psis_tail_lds_bytes(t.P);
-    hipLaunchKernelGGL(psis_tail_kernel<true>, dim3((unsigned)Nb), dim3(kPsisBlock), lds, stream, ll, S, Nb, C, t.M,
-                       t.P, t.keys, t.idx, t.xs, t.meta);
+    hipLaunchKernelGGL((psis_tail_kernel<true, kRatio>), dim3((unsigned)Nb), dim3(kPsisBlock), lds, stream, ll, S, Nb,
+                       C, t.M, t.P, t.keys, t.idx, t.xs, t.meta);
   } else {
-    hipLaunchKernelGGL(psis_tail_kernel<false>, dim3((unsigned)Nb), dim3(kPsisBlock), 0, stream, ll, S, Nb, C, t.M,
-                       t.P, t.keys, t.idx, t.xs, t.meta);
+    hipLaunchKernelGGL((psis_tail_kernel<false, kRatio>), dim3((unsigned)Nb), dim3(kPsisBlock), 0, stream, ll, S, Nb,
+                       C, t.M, t.P, t.keys, t.idx, t.xs, t.meta);
   }
   HIP_TRY(hipGetLastError());
   return EXMC_OK;
@@ -2842,6 +2845,272 @@ int exmc_hip_advi_host(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int 
   fits_first(sc.host(s_iters), num_iters, 1, C);
   fits_first(sc.host(s_conv), converged, 1, C);
   return EXMC_OK;
+}
+
+}  // extern "C"
+
+// ---- importance diagnostics of the fits (include/exmc_hip_fit_psis.h; exmc_fit_psis.hpp, exmc_psis_ratio.hpp) ----
+namespace {
+
+int fit_lr_check(exmc_hip_model* m, const void* draws, const void* mu, const void* scale, int scale_kind, int n_draws,
+                 int d, int n_fits) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  if (!draws || !mu || !scale || (scale_kind != EXMC_FIT_SIGMA && scale_kind != EXMC_FIT_LOG_SIGMA) || n_draws < 1 ||
+      n_fits < 1 || d != m->d)
+    return fail(EXMC_ERR_BADARG, "fit psis: bad arguments");
+  return EXMC_OK;
+}
+
+// fit_log_ratio_kernel of the handle's layout on its stream; the caller records the events
+int fit_lr_launch(exmc_hip_model* m, const double* draws, const double* mu, const double* scale, int scale_kind,
+                  int n_draws, int n_fits, int lanes_per_chain, double* lr, double* logp) {
+  static_assert(EXMC_FIT_SIGMA == kFitSigma && EXMC_FIT_LOG_SIGMA == kFitLogSigma, "the header states the kernel's kinds");
+  FitLogRatioParams P;
+  P.draws = draws;
+  P.mu = mu;
+  P.scale = scale;
+  P.scale_kind = scale_kind;
+  P.n_draws = n_draws;
+  P.n_fits = n_fits;
+  P.log_norm = 0.5 * m->d * std::log(2.0 * M_PI);
+  P.lr = lr;
+  P.logp = logp;
+  return dispatch(m, resolve_lanes(m, lanes_per_chain), [&](auto tag, const auto& mc) {
+    using T = decltype(tag);
+    const size_t xlds = aux_lds_bytes<typename T::M>();
+    EXMC_KLAUNCH(m->device, (fit_log_ratio_kernel<typename T::M, T::G>), grid_for(n_fits, T::G, kBlock), dim3(kBlock),
+                 xlds, m->stream, P, mc);
+    HIP_TRY(hipGetLastError());
+    return (int)EXMC_OK;
+  });
+}
+
+int ratio_check(const void* lr, int n_draws, int n_fits, int pooled, int n_resample, const void* out,
+                const void* idx) {
+  if (!lr || !out || n_draws < 1 || n_fits < 1 || n_resample < 0 || (n_resample > 0 && !idx))
+    return fail(EXMC_ERR_BADARG, "fit psis: bad arguments");
+  if (pooled && (long long)n_draws * n_fits > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "fit psis: more than 2^31 - 1 pooled samples");
+  return EXMC_OK;
+}
+
+#ifndef EXMC_ONLY_CUSTOM
+// the scratch of the smoothing and the resampling of lr[S][F] in one view, and their launches
+struct RatioScratch {
+  PsisScratch ps;
+  CallBuf l1, xs, r, tot, base;
+  int S = 0, Nb = 0, C = 0, n_blocks = 0;
+  // the view; `need_xs`: no caller's lw to hold the smoothed values, and the resampling reads them
+  int alloc(int n_draws, int n_fits, int pooled, int n_resample, bool need_xs) {
+    S = n_draws;
+    Nb = pooled ? 1 : n_fits;
+    C = pooled ? n_fits : 1;
+    const long long n = (long long)S * C;
+    n_blocks = (int)((n + kRatioScan - 1) / kRatioScan);
+    static_assert(kRatioFields <= kPsisFields, "the chunk states fit PsisScratch::part");
+    int rc = ps.alloc(S, C, Nb);
+    if (!rc) rc = l1.alloc((size_t)Nb * 8);
+    if (!rc && need_xs) rc = xs.alloc((size_t)S * n_fits * 8);
+    if (!rc && n_resample > 0) rc = r.alloc((size_t)S * n_fits * 8);
+    if (!rc && n_resample > 0) rc = tot.alloc((size_t)n_blocks * Nb * 8);
+    if (!rc && n_resample > 0) rc = base.alloc(((size_t)n_blocks + 1) * Nb * 8);
+    if (rc) return rc;
+    if (ps.P <= kPsisLdsPairs && psis_tail_lds_bytes(ps.P) > 40 * 1024)   // as PsisScratch::alloc, for this instantiation
+      EXMC_KMAXLDS((psis_tail_kernel<true, true>), psis_tail_lds_bytes(ps.P));
+    return EXMC_OK;
+  }
+};
+
+int ratio_launch(hipStream_t stream, const RatioScratch& sc, const double* lr, int n_resample, uint64_t seed,
+                 double* out, double* lw, int32_t* idx) {
+  const int S = sc.S, Nb = sc.Nb, C = sc.C;
+  const long long n = (long long)S * C, total = n * Nb;
+  const PsisTables t = psis_tables(sc.ps);
+  const IcGrid g = sc.ps.g;
+  double* part = sc.ps.part.as<double>();
+  double* x = lw ? lw : sc.xs.as<double>();   // null: nobody reads the weights
+  int rc = psis_tails<true>(stream, t, lr, S, Nb, C);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ratio_weights_kernel, dim3((unsigned)g.n_chunks, (unsigned)g.yblocks), dim3(g.block), 0, stream,
+                     lr, S, Nb, C, g.chunk, t.P, t.keys, t.idx, t.xs, t.meta, part, x);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ratio_merge_kernel, dim3((unsigned)((Nb + 255) / 256)), dim3(256), 0, stream, part, g.n_chunks, n,
+                     Nb, t.meta, out, sc.l1.as<double>());
+  HIP_TRY(hipGetLastError());
+  if (!x) return EXMC_OK;
+  hipLaunchKernelGGL(ratio_normalise_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, total, Nb,
+                     C, sc.l1.as<double>());
+  HIP_TRY(hipGetLastError());
+  if (n_resample < 1) return EXMC_OK;
+  const long long lanes = (long long)Nb * sc.n_blocks;
+  hipLaunchKernelGGL(ratio_scan_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, x, S, Nb, C,
+                     sc.n_blocks, sc.r.as<double>(), sc.tot.as<double>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ratio_resample_kernel, dim3((unsigned)Nb), dim3(kRatioBlock), 0, stream, sc.r.as<double>(),
+                     sc.tot.as<double>(), sc.base.as<double>(), S, Nb, C, sc.n_blocks, n_resample, seed,
+                     sc.l1.as<double>(), idx);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+
+int gather_launch(hipStream_t stream, const double* draws, const int32_t* idx, int n_draws, int d, int n_fits,
+                  int pooled, int n_resample, double* out) {
+  const long long total = (long long)n_resample * d * (pooled ? 1 : n_fits);
+  hipLaunchKernelGGL(ratio_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, draws, idx,
+                     n_draws, d, n_fits, pooled ? 1 : 0, n_resample, out);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+#endif
+
+}  // namespace
+
+extern "C" {
+
+int exmc_hip_fit_log_ratio(exmc_hip_model* m, const double* draws_dev, const double* mu_dev, const double* scale_dev,
+                           int scale_kind, int n_draws, int d, int n_fits, int lanes_per_chain, double* lr_dev,
+                           double* logp_dev) {
+  int rc = fit_lr_check(m, draws_dev, mu_dev, scale_dev, scale_kind, n_draws, d, n_fits);
+  if (rc) return rc;
+  if (!lr_dev) return fail(EXMC_ERR_BADARG, "fit psis: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  rc = fit_lr_launch(m, draws_dev, mu_dev, scale_dev, scale_kind, n_draws, n_fits, lanes_per_chain, lr_dev, logp_dev);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the launch
+}
+
+int exmc_hip_ratio_psis_from_lr(int device, const double* lr_dev, int n_draws, int n_fits, int pooled, int n_resample,
+                                uint64_t seed, double* out_dev, double* lw_dev, int32_t* idx_dev) {
+  int rc = ratio_check(lr_dev, n_draws, n_fits, pooled, n_resample, out_dev, idx_dev);
+  if (rc) return rc;
+  rc = select_device(device);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)seed; (void)lw_dev;
+  return fail(EXMC_ERR_UNSUPPORTED, "fit psis: use libexmc_hip.so for the model-free smoothing and resampling");
+#else
+  RatioScratch sc;
+  rc = sc.alloc(n_draws, n_fits, pooled, n_resample, !lw_dev && n_resample > 0);
+  if (!rc) rc = ratio_launch((hipStream_t)0, sc, lr_dev, n_resample, seed, out_dev, lw_dev, idx_dev);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)0));
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_ratio_gather(int device, const double* draws_dev, const int32_t* idx_dev, int n_draws, int d, int n_fits,
+                          int pooled, int n_resample, double* out_dev) {
+  if (!draws_dev || !idx_dev || !out_dev || n_draws < 1 || d < 1 || n_fits < 1 || n_resample < 1)
+    return fail(EXMC_ERR_BADARG, "fit psis: bad arguments");
+  if (pooled && (long long)n_draws * n_fits > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "fit psis: more than 2^31 - 1 pooled samples");
+  int rc = select_device(device);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  return fail(EXMC_ERR_UNSUPPORTED, "fit psis: use libexmc_hip.so for the model-free smoothing and resampling");
+#else
+  rc = gather_launch((hipStream_t)0, draws_dev, idx_dev, n_draws, d, n_fits, pooled, n_resample, out_dev);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)0));
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_fit_psis(exmc_hip_model* m, const double* draws_dev, const double* mu_dev, const double* scale_dev,
+                      int scale_kind, int n_draws, int d, int n_fits, int lanes_per_chain, int pooled, int n_resample,
+                      uint64_t seed, double* out_dev, double* lw_dev, int32_t* idx_dev, double* resampled_dev,
+                      double* lr_dev, double* logp_dev) {
+  int rc = fit_lr_check(m, draws_dev, mu_dev, scale_dev, scale_kind, n_draws, d, n_fits);
+  if (rc) return rc;
+  if (!out_dev || n_resample < 0) return fail(EXMC_ERR_BADARG, "fit psis: bad arguments");
+  if (pooled && (long long)n_draws * n_fits > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "fit psis: more than 2^31 - 1 pooled samples");
+#ifdef EXMC_ONLY_CUSTOM
+  (void)lanes_per_chain; (void)seed; (void)lw_dev; (void)idx_dev; (void)resampled_dev; (void)lr_dev; (void)logp_dev;
+  return fail(EXMC_ERR_UNSUPPORTED, "fit psis: a generated model goes through exmc_hip_fit_log_ratio and "
+              "libexmc_hip.so's exmc_hip_ratio_psis_from_lr");
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t G = pooled ? 1 : (size_t)n_fits;
+  RatioScratch sc;
+  CallBuf lr_own, idx_own;
+  if (!lr_dev) {
+    rc = lr_own.alloc((size_t)n_draws * n_fits * 8);
+    if (rc) return rc;
+    lr_dev = lr_own.as<double>();
+  }
+  if (n_resample > 0 && !idx_dev) {
+    rc = idx_own.alloc((size_t)n_resample * G * 4);
+    if (rc) return rc;
+    idx_dev = idx_own.as<int32_t>();
+  }
+  rc = sc.alloc(n_draws, n_fits, pooled, n_resample, !lw_dev && n_resample > 0);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  rc = fit_lr_launch(m, draws_dev, mu_dev, scale_dev, scale_kind, n_draws, n_fits, lanes_per_chain, lr_dev, logp_dev);
+  if (!rc) rc = ratio_launch(m->stream, sc, lr_dev, n_resample, seed, out_dev, lw_dev, idx_dev);
+  if (!rc && n_resample > 0 && resampled_dev)
+    rc = gather_launch(m->stream, draws_dev, idx_dev, n_draws, d, n_fits, pooled, n_resample, resampled_dev);
+  if (rc) {
+    (void)hipStreamSynchronize(m->stream);   // the scratch is freed on return
+    return rc;
+  }
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the launches: before the scratch is freed
+#endif
+}
+
+int exmc_hip_fit_psis_host(exmc_hip_model* m, const double* draws, const double* mu, const double* scale,
+                           int scale_kind, int n_draws, int d, int n_fits, int lanes_per_chain, int pooled,
+                           int n_resample, uint64_t seed, double* out, double* lw, int32_t* idx, double* resampled,
+                           double* lr, double* logp) {
+  int rc = fit_lr_check(m, draws, mu, scale, scale_kind, n_draws, d, n_fits);
+  if (rc) return rc;
+  if (!out || n_resample < 0) return fail(EXMC_ERR_BADARG, "fit psis: bad arguments");
+  if (pooled && (long long)n_draws * n_fits > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "fit psis: more than 2^31 - 1 pooled samples");
+#ifdef EXMC_ONLY_CUSTOM
+  (void)lanes_per_chain; (void)seed; (void)lw; (void)idx; (void)resampled; (void)lr; (void)logp;
+  return fail(EXMC_ERR_UNSUPPORTED, "fit psis: a generated model goes through exmc_hip_fit_log_ratio and "
+              "libexmc_hip.so's exmc_hip_ratio_psis_from_lr");
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t C = (size_t)n_fits, D = (size_t)d, S = (size_t)n_draws, R = (size_t)n_resample;
+  const size_t G = pooled ? 1 : C;
+  Scratch sc;
+  const auto s_mu = sc.take<double>(D * C), s_scale = sc.take<double>(D * C);
+  const auto s_out = sc.take<double>((size_t)EXMC_FIT_PSIS_NOUT * G);
+  const auto s_lw = sc.take<double>(S * C), s_lr = sc.take<double>(S * C), s_logp = sc.take<double>(S * C);
+  const auto s_res = sc.take<double>(R * D * G);
+  const auto s_idx = sc.take<int32_t>(R * G);
+  rc = sc.alloc_with_trace(draws, n_draws, d, n_fits);
+  if (rc) return rc;
+  {
+    std::vector<double> h(2 * D * C);   // [C][d] -> [d][C]
+    for (size_t c = 0; c < C; c++)
+      for (size_t i = 0; i < D; i++) {
+        h[i * C + c] = mu[c * D + i];
+        h[D * C + i * C + c] = scale[c * D + i];
+      }
+    HIP_TRY(hipMemcpy(sc.dev(s_mu), h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  }
+  rc = exmc_hip_fit_psis(m, sc.trace(), sc.dev(s_mu), sc.dev(s_scale), scale_kind, n_draws, d, n_fits, lanes_per_chain,
+                         pooled, n_resample, seed, sc.dev(s_out), sc.dev(s_lw), R ? sc.dev(s_idx) : nullptr,
+                         R ? sc.dev(s_res) : nullptr, sc.dev(s_lr), sc.dev(s_logp));
+  if (!rc) rc = sc.download();
+  if (rc) return rc;
+  std::copy(sc.host(s_out), sc.host(s_out) + (size_t)EXMC_FIT_PSIS_NOUT * G, out);
+  fits_first(sc.host(s_lw), lw, S, C);
+  fits_first(sc.host(s_lr), lr, S, C);
+  fits_first(sc.host(s_logp), logp, S, C);
+  if (R) {
+    fits_first(sc.host(s_idx), idx, R, G);                                                 // [R][G] -> [G][R]
+    if (resampled) transpose_trace_vec(sc.host(s_res), resampled, n_resample, d, (int)G);   // [R][d][G] -> [G][R][d]
+  }
+  return EXMC_OK;
+#endif
 }
 
 // ---- posterior predictive (include/exmc_hip_predictive.h; predictive_kernel, exmc_predictive.hpp) ------

@@ -96,7 +96,10 @@ __device__ __forceinline__ double psis_tail_sum(const double* t, int T, double b
 
 // kLds: the pairs (and then t) live in dynamic LDS, keys [P] then indices [P]; else in the datum's
 // table rows, t in its row of tab_xs. P is a power of two >= M, the row length of the tables.
-template <bool kLds>
+// kRatio (exmc_psis_ratio.hpp): `ll` holds log ratios lr themselves, read as ll = -lr. A ratio of -inf
+// is admitted -- it counts in n, x = -inf lies below every cutoff and never enters the tail -- and a
+// group with a NaN or +inf ratio, or without a finite one, is the one whose outputs are NaN.
+template <bool kLds, bool kRatio = false>
 __global__ __launch_bounds__(kPsisBlock) void psis_tail_kernel(const double* __restrict__ ll, int S, int Nb, int C,
                                                               int M, int P, uint64_t* __restrict__ tab_keys,
                                                               uint32_t* __restrict__ tab_idx,
@@ -123,8 +126,8 @@ __global__ __launch_bounds__(kPsisBlock) void psis_tail_kernel(const double* __r
   int bad = 0;
   PsisWalk w0(ll, Nb, C, i, tid);
   for (unsigned k = tid; k < n; k += kPsisBlock, w0.next()) {
-    const double v = w0.get();
-    if (!exmc_isfinite(v)) bad = 1;
+    const double v = kRatio ? -w0.get() : w0.get();
+    if (kRatio ? (!(v == v) || v == -__builtin_inf()) : !exmc_isfinite(v)) bad = 1;
     mx = fmax(mx, -v);
   }
   for (int o = 32; o >= 1; o >>= 1) {
@@ -145,6 +148,7 @@ __global__ __launch_bounds__(kPsisBlock) void psis_tail_kernel(const double* __r
     mx = fmax(mx, red[w]);
     bad |= redi[w];
   }
+  if (kRatio && mx == -__builtin_inf()) bad = 1;   // no finite ratio
   if (bad) {
     if (tid == 0) {
       mt[0] = mx; mt[1] = 0.0; mt[2] = 0.0; mt[3] = exmc_from_bits(EXMC_NAN_BITS); mt[4] = 0.0; mt[5] = 1.0;
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(kPsisBlock) void psis_tail_kernel(const double* __r
     const unsigned long long prefix = sel_prefix;
     PsisWalk wk(ll, Nb, C, i, tid);
     for (unsigned k = tid; k < n; k += kPsisBlock, wk.next()) {
-      const uint64_t key = psis_key(-wk.get() - mx);
+      const uint64_t key = psis_key((kRatio ? wk.get() : -wk.get()) - mx);
       if (done == 0 || (key >> (shift + w)) == prefix) atomicAdd(&hist[(unsigned)(key >> shift) & (nb - 1)], 1u);
     }
     __syncthreads();
@@ -189,7 +193,7 @@ __global__ __launch_bounds__(kPsisBlock) void psis_tail_kernel(const double* __r
   // 3. the tail, compacted and sorted by (x, k)
   PsisWalk wt(ll, Nb, C, i, tid);
   for (unsigned k = tid; k < n; k += kPsisBlock, wt.next()) {
-    const double x = -wt.get() - mx;
+    const double x = (kRatio ? wt.get() : -wt.get()) - mx;
     if (x > cutoff) {
       const unsigned pos = atomicAdd(&tail_cnt, 1u);
       if (pos < (unsigned)P) {

@@ -69,3 +69,15 @@ def fit(ir_or_compiled, opts=None, num_paths=1):
         return draws[0], infos[0]
     elbo = np.where(np.isfinite(raw["elbo"]), raw["elbo"], -np.inf)
     return draws, infos, int(np.argmax(elbo))
+
+
+def fit_psis(ir_or_compiled, opts=None, num_paths=1, pooled=False, num_resample=0, resample_seed=0):
+    """fit_raw, then importance.psis_fit over its paths: the Pareto k of every fit (or of the pool), the
+    smoothed log weights and, with num_resample > 0, the importance-resampled draws. Returns (raw, result)."""
+    o = _validate(opts, num_paths)
+    from . import importance, sampler
+    compiled = ir_or_compiled if isinstance(ir_or_compiled, sampler.Compiled) else \
+        sampler.Compiled(ir_or_compiled, device=o.get("device", 0))
+    raw = fit_raw(compiled, o, num_paths)
+    return raw, importance.psis_fit(compiled, raw, pooled=pooled, num_resample=num_resample, seed=resample_seed,
+                                    lanes_per_chain=int(o.get("lanes_per_chain") or 0))
