@@ -1,5 +1,5 @@
 /* erl_nif_decl.h -- declarations of the part of OTP's public NIF API (erts/emulator/beam/erl_nif.h,
- * documented in the erl_nif(3) manual page) that the two shims in this directory use.
+ * documented in the erl_nif(3) manual page) that the shims in this directory use.
  *
  * Why this file exists: the build image has no Erlang/OTP, so the real <erl_nif.h> is absent. These
  * are DECLARATIONS ONLY, written from the public manual page, so that `gcc -c` type-checks the shims

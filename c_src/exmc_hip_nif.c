@@ -28,7 +28,6 @@
 #include <time.h>
 
 static ErlNifResourceType* MODEL_RT;
-static int g_device = 0;
 
 /* The entry points of include/exmc_hip.h this module calls, as a table: the library this shim is
  * linked against fills one (g_base); a generated model's plug-in library (a build of the same
@@ -80,9 +79,7 @@ static const exmc_api g_base = {
 
 /* {:exmc_hip_error, code, message} with the message of the library the handle belongs to */
 static ERL_NIF_TERM raise_api(ErlNifEnv* env, const exmc_api* A, int rc) {
-  if (rc == EXMC_ERR_BADARG) return enif_make_badarg(env);
-  return enif_raise_exception(env, tuple3(env, enif_make_atom(env, "exmc_hip_error"), enif_make_int(env, rc),
-                                          enif_make_string(env, A->last_error(), ERL_NIF_LATIN1)));
+  return raise_msg(env, rc, A->last_error());
 }
 
 /* tid / has_tid: the sender thread of the last stream_run. ERTS threads are joinable and must be
@@ -258,19 +255,12 @@ static ERL_NIF_TERM model_create_plugin(ErlNifEnv* env, int argc, const ERL_NIF_
  * the r-th id of Enum.sort_by(& &1.id), point_map.ex:37) */
 static ERL_NIF_TERM model_set_flat_order(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   HANDLE(argv[0]);
-  unsigned len;
+  int32_t* perm;
   (void)argc;
-  if (!m || !enif_get_list_length(env, argv[1], &len) || (int)len != A->model_dim(m))
-    return enif_make_badarg(env);
-  int32_t* perm = (int32_t*)enif_alloc((len ? len : 1) * sizeof(int32_t));
-  ERL_NIF_TERM head, tail = argv[1];
-  int ok = 1;
-  for (unsigned i = 0; i < len && ok; i++) {
-    int v;
-    ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_int(env, head, &v);
-    perm[i] = v;
-  }
-  int rc = ok ? A->model_set_flat_order(m, perm, (int)len) : EXMC_ERR_BADARG;
+  if (!m) return enif_make_badarg(env);
+  const int d = A->model_dim(m);
+  if (!get_i32_list(env, argv[1], (unsigned)d, &perm)) return enif_make_badarg(env);
+  int rc = A->model_set_flat_order(m, perm, d);
   enif_free(perm);
   return rc == EXMC_OK ? enif_make_atom(env, "ok") : raise_api(env, A, rc);
 }
@@ -799,8 +789,7 @@ static ErlNifFunc nif_funcs[] = {
 static int on_load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
-  const char* dev = getenv("EXMC_HIP_DEVICE");
-  g_device = dev ? atoi(dev) : 0;
+  g_device = env_device();
   g_tid_lock = enif_mutex_create((char*)"exmc_hip_tid");
   g_reap = NULL;
   MODEL_RT = enif_open_resource_type(env, NULL, "exmc_hip_model", model_dtor, ERL_NIF_RT_CREATE, NULL);

@@ -8,8 +8,8 @@
  *              (f64, kernel order, unconstrained), num_iters_bin, best_index_bin, status_bin [path] (i32)}
  *          (exmc_hip_pathfinder_host; path c has seed + 7919 (chain_lo + c))
  *
- * Written the way exmc_hip_psis_nif.c is, and a module beside it: the call makes a handle of its own
- * from the model's kind and data and destroys it before it returns. Conventions as exmc_hip_nif.c:
+ * A per-call module on the frame of exmc_nif_util.h: the call makes a handle of its own from the model's
+ * kind and data and destroys it before it returns. Conventions as exmc_hip_nif.c:
  * native-endian binaries, a decode failure is a badarg, a failed library call raises
  * {:exmc_hip_error, code, message} (a kind or lane count without a compiled layout: code 4), a dirty
  * IO-bound job. */
@@ -17,38 +17,28 @@
 
 #include "../include/exmc_hip_pathfinder.h"
 
-static int g_device = 0;
-
 static ERL_NIF_TERM fit(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  const ERL_NIF_TERM* model;
-  int arity, kind, n_paths, chain_lo, num_draws, max_iters, history, lanes;
-  const double* data;
-  size_t nd;
+  nif_model model;
+  int n_paths, chain_lo, num_draws, max_iters, history, lanes, d;
   unsigned plen;
   ErlNifUInt64 seed;
   (void)argc;
-  if (!enif_get_tuple(env, argv[0], &arity, &model) || arity != 2 || !enif_get_int(env, model[0], &kind) ||
-      !get_f64_bin(env, model[1], &data, &nd) || !enif_get_list_length(env, argv[1], &plen) ||
+  if (!get_model(env, argv[0], &model) || !enif_get_list_length(env, argv[1], &plen) ||
       !enif_get_int(env, argv[2], &n_paths) || !enif_get_int(env, argv[3], &chain_lo) ||
       !enif_get_int(env, argv[4], &num_draws) || !enif_get_int(env, argv[5], &max_iters) ||
       !enif_get_int(env, argv[6], &history) || !enif_get_uint64(env, argv[7], &seed) ||
       !enif_get_int(env, argv[8], &lanes) || n_paths < 1 || num_draws < 1 || chain_lo < 0 || lanes < 0)
     return enif_make_badarg(env);
   exmc_hip_model* m = NULL;
-  int rc = exmc_hip_model_create(kind, 0, data, (int)nd, g_device, &m);
+  int rc = model_open(&model, g_device, &m, &d, NULL);
   if (rc != EXMC_OK) return raise_hip(env, rc);
-  const int d = exmc_hip_model_dim(m);
-  if (plen != 0) {
-    int32_t* perm = (int32_t*)enif_alloc(plen * sizeof(int32_t));
-    ERL_NIF_TERM head, tail = argv[1];
-    int ok = (int)plen == d;
-    for (unsigned i = 0; i < plen && ok; i++) {
-      int v;
-      ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_int(env, head, &v);
-      perm[i] = ok ? v : 0;
+  if (plen != 0) {   /* []: the kernel order is the flat order, no call */
+    int32_t* perm;
+    rc = EXMC_ERR_BADARG;
+    if (get_i32_list(env, argv[1], (unsigned)d, &perm)) {
+      rc = exmc_hip_model_set_flat_order(m, perm, d);
+      enif_free(perm);
     }
-    rc = ok ? exmc_hip_model_set_flat_order(m, perm, d) : EXMC_ERR_BADARG;
-    enif_free(perm);
     if (rc != EXMC_OK) {
       exmc_hip_model_destroy(m);
       return raise_hip(env, rc);
@@ -78,13 +68,4 @@ static ErlNifFunc nif_funcs[] = {
     {"fit", 9, fit, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
-static int on_load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
-  (void)env;
-  (void)priv;
-  (void)info;
-  const char* dev = getenv("EXMC_HIP_DEVICE");
-  g_device = dev ? atoi(dev) : 0;
-  return 0;
-}
-
-ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPathfinderNative, nif_funcs, on_load, NULL, NULL, NULL)
+ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPathfinderNative, nif_funcs, load_device, NULL, NULL, NULL)

@@ -8,8 +8,8 @@
  *           -> yrep_bin [chain][draw][datum] (f64; datums in the kind's data order)
  *           (exmc_hip_posterior_predictive_host; chain c draws with seed + 7919 (chain_lo + c))
  *
- * Written the way exmc_hip_compare_nif.c is, and a module beside it: the call makes a handle of its own
- * from the model's kind and data and destroys it before it returns. Conventions as exmc_hip_nif.c:
+ * A per-call module on the frame of exmc_nif_util.h: the call makes a handle of its own from the model's
+ * kind and data and destroys it before it returns. Conventions as exmc_hip_nif.c:
  * native-endian f64 binaries, a decode failure is a badarg, a failed library call raises
  * {:exmc_hip_error, code, message} (a kind without datums: code 4), a dirty IO-bound job. */
 #include "exmc_nif_util.h"
@@ -17,28 +17,23 @@
 #include "../include/exmc_hip_compare.h"
 #include "../include/exmc_hip_predictive.h"
 
-static int g_device = 0;
-
 static ERL_NIF_TERM posterior_predictive(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  const ERL_NIF_TERM* model;
-  int arity, kind, c, s;
-  const double *data, *draws;
-  size_t nd, n;
+  nif_model model;
+  int c, s, d, N;
+  const double* draws;
+  size_t n;
   ErlNifUInt64 seed;
   exmc_hip_predictive_opts o;
   (void)argc;
-  if (!enif_get_tuple(env, argv[0], &arity, &model) || arity != 2 || !enif_get_int(env, model[0], &kind) ||
-      !get_f64_bin(env, model[1], &data, &nd) || !get_f64_bin(env, argv[1], &draws, &n) ||
+  if (!get_model(env, argv[0], &model) || !get_f64_bin(env, argv[1], &draws, &n) ||
       !enif_get_int(env, argv[2], &c) || !enif_get_int(env, argv[3], &s) || !enif_get_uint64(env, argv[4], &seed) ||
       !enif_get_int(env, argv[5], &o.chain_lo) || c < 1 || s < 1 || o.chain_lo < 0)
     return enif_make_badarg(env);
   o.seed = (uint64_t)seed;
   o.resume = 0;
   exmc_hip_model* m = NULL;
-  int rc = exmc_hip_model_create(kind, 0, data, (int)nd, g_device, &m);
+  int rc = model_open(&model, g_device, &m, &d, &N);
   if (rc != EXMC_OK) return raise_hip(env, rc);
-  const int d = exmc_hip_model_dim(m);
-  const int N = exmc_hip_model_n_data(m);
   ERL_NIF_TERM out = 0;
   if (n != (size_t)c * (size_t)s * (size_t)d) {
     rc = EXMC_ERR_BADARG;
@@ -57,13 +52,4 @@ static ErlNifFunc nif_funcs[] = {
     {"posterior_predictive", 6, posterior_predictive, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
-static int on_load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
-  (void)env;
-  (void)priv;
-  (void)info;
-  const char* dev = getenv("EXMC_HIP_DEVICE");
-  g_device = dev ? atoi(dev) : 0;
-  return 0;
-}
-
-ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPredictiveNative, nif_funcs, on_load, NULL, NULL, NULL)
+ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPredictiveNative, nif_funcs, load_device, NULL, NULL, NULL)

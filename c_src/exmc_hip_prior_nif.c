@@ -10,8 +10,8 @@
  *           replicates = 0 (then no datum is drawn and the generators do not advance for them)
  *           (exmc_hip_prior_samples_host; chain c draws with seed + 7919 (chain_lo + c))
  *
- * Written the way exmc_hip_predictive_nif.c is, and a module beside it: the call makes a handle of its own
- * from the model's kind and data and destroys it before it returns. Conventions as exmc_hip_nif.c:
+ * A per-call module on the frame of exmc_nif_util.h: the call makes a handle of its own from the model's
+ * kind and data and destroys it before it returns. Conventions as exmc_hip_nif.c:
  * native-endian f64 binaries, a decode failure is a badarg, a failed library call raises
  * {:exmc_hip_error, code, message} (a kind without a prior walk: code 4), a dirty IO-bound job. */
 #include "exmc_nif_util.h"
@@ -19,28 +19,21 @@
 #include "../include/exmc_hip_compare.h"
 #include "../include/exmc_hip_prior.h"
 
-static int g_device = 0;
-
 static ERL_NIF_TERM prior_samples(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  const ERL_NIF_TERM* model;
-  int arity, kind, c, s, rep;
-  const double* data;
-  size_t nd;
+  nif_model model;
+  int c, s, rep, d, N;
   ErlNifUInt64 seed;
   exmc_hip_predictive_opts o;
   (void)argc;
-  if (!enif_get_tuple(env, argv[0], &arity, &model) || arity != 2 || !enif_get_int(env, model[0], &kind) ||
-      !get_f64_bin(env, model[1], &data, &nd) || !enif_get_int(env, argv[1], &c) || !enif_get_int(env, argv[2], &s) ||
+  if (!get_model(env, argv[0], &model) || !enif_get_int(env, argv[1], &c) || !enif_get_int(env, argv[2], &s) ||
       !enif_get_uint64(env, argv[3], &seed) || !enif_get_int(env, argv[4], &o.chain_lo) ||
       !enif_get_int(env, argv[5], &rep) || c < 1 || s < 1 || o.chain_lo < 0 || (rep != 0 && rep != 1))
     return enif_make_badarg(env);
   o.seed = (uint64_t)seed;
   o.resume = 0;
   exmc_hip_model* m = NULL;
-  int rc = exmc_hip_model_create(kind, 0, data, (int)nd, g_device, &m);
+  int rc = model_open(&model, g_device, &m, &d, &N);
   if (rc != EXMC_OK) return raise_hip(env, rc);
-  const int d = exmc_hip_model_dim(m);
-  const int N = exmc_hip_model_n_data(m);
   ERL_NIF_TERM out[3] = {0, 0, 0};
   if (N < 0) {
     double none = 0.0;   /* EXMC_ERR_UNSUPPORTED and its message */
@@ -60,13 +53,4 @@ static ErlNifFunc nif_funcs[] = {
     {"prior_samples", 6, prior_samples, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
-static int on_load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
-  (void)env;
-  (void)priv;
-  (void)info;
-  const char* dev = getenv("EXMC_HIP_DEVICE");
-  g_device = dev ? atoi(dev) : 0;
-  return 0;
-}
-
-ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPriorNative, nif_funcs, on_load, NULL, NULL, NULL)
+ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPriorNative, nif_funcs, load_device, NULL, NULL, NULL)

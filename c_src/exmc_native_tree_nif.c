@@ -29,7 +29,6 @@
 #include "exmc_nif_util.h"
 
 static ErlNifResourceType* TRAJ_RT;
-static int g_device = 0;   /* EXMC_HIP_DEVICE at load */
 
 typedef struct {
   exmc_hip_traj* t;
@@ -356,8 +355,7 @@ static ErlNifFunc nif_funcs[] = {
 static int on_load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
-  const char* dev = getenv("EXMC_HIP_DEVICE");
-  g_device = dev ? atoi(dev) : 0;
+  g_device = env_device();
   TRAJ_RT = enif_open_resource_type(env, NULL, "exmc_hip_traj", traj_dtor, ERL_NIF_RT_CREATE, NULL);
   return TRAJ_RT ? 0 : 1;
 }

@@ -11,7 +11,7 @@
 #include <string.h>
 #include <time.h>
 
-#include "../../include/exmc_hip.h"
+#include "../../include/exmc_hip_compare.h"   /* exmc_hip.h, and exmc_hip_model_n_data */
 
 struct exmc_hip_model {
   int d;
@@ -53,6 +53,7 @@ void exmc_hip_model_destroy(exmc_hip_model* m) {
   free(m);
 }
 int exmc_hip_model_dim(const exmc_hip_model* m) { return m ? m->d : -1; }
+int exmc_hip_model_n_data(const exmc_hip_model* m) { return m ? 2 * m->d : -1; }   /* the per-call frame reads it */
 int exmc_hip_model_set_flat_order(exmc_hip_model* m, const int32_t* p, int d) { (void)m; (void)p; (void)d; return EXMC_OK; }
 int exmc_hip_model_set_dense_mass(exmc_hip_model* m, const double* a, const double* b, int d) { (void)m; (void)a; (void)b; (void)d; return EXMC_OK; }
 int exmc_hip_model_clear_dense_mass(exmc_hip_model* m) { (void)m; return EXMC_OK; }

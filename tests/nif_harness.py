@@ -1,6 +1,6 @@
 """Loads the NIF shims of c_src/ without a BEAM: builds tests/host/fake_erl_nif.c (the enif_*
-functions declared in c_src/erl_nif_decl.h over a flat term table) and the two shims against
-libexmc_hip.so, and converts between Python values and the fake runtime's terms. Test
+functions declared in c_src/erl_nif_decl.h over a flat term table) and any shim (load_shim) against
+libexmc_hip.so, and converts between Python values and the fake runtime's terms (tuple_term: a tuple). Test
 infrastructure only."""
 import ctypes as C
 import os
@@ -42,25 +42,22 @@ class BadArg(Exception):
 _cache = {}
 
 
+def _sanitize_flags():
+    # EXMC_SANITIZE=address,undefined (tools/sanitize_cpu.sh, with libasan preloaded into the interpreter):
+    # the shims and the term table are built with the sanitizers
+    san = os.environ.get("EXMC_SANITIZE")
+    return ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-g"] if san else []
+
+
 def build(outdir):
+    """(F, {"NativeTree": Module, "HipNative": Module}): the fake runtime and the two shims that hold resources."""
     # ONE term table per process: the fake runtime is loaded RTLD_GLOBAL (the shims resolve their
     # enif_* calls against it), so a second copy would split the state between two libraries
     if _cache:
         return next(iter(_cache.values()))
     fake = os.path.join(outdir, "libfake_erl_nif.so")
-    # EXMC_SANITIZE=address,undefined (tools/sanitize_cpu.sh, with libasan preloaded into the interpreter):
-    # the shims and the term table are built with the sanitizers
-    san = os.environ.get("EXMC_SANITIZE")
-    sflags = ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-g"] if san else []
-    subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-fPIC", "-shared", "-pthread"] + sflags +
+    subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-fPIC", "-shared", "-pthread"] + _sanitize_flags() +
                           ["-o", fake, os.path.join(ROOT, "tests", "host", "fake_erl_nif.c")])
-    shims = {}
-    for mod, src in (("NativeTree", "exmc_native_tree_nif.c"), ("HipNative", "exmc_hip_nif.c")):
-        so = os.path.join(outdir, "lib%s_nif.so" % mod)
-        subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared"] + sflags +
-                              ["-o", so, os.path.join(ROOT, "c_src", src), "-L" + LIBDIR, "-lexmc_hip",
-                               "-Wl,-rpath," + LIBDIR, "-Wl,-z,lazy", "-ldl"])
-        shims[mod] = so
     F = C.CDLL(fake, mode=os.RTLD_GLOBAL | os.RTLD_NOW)
     tt = C.c_ulong
     F.fk_atom.argtypes = [C.c_char_p]; F.fk_atom.restype = tt
@@ -83,13 +80,32 @@ def build(outdir):
     F.fk_mailbox_len.restype = C.c_size_t
     F.fk_mailbox_get.argtypes = [C.c_size_t]; F.fk_mailbox_get.restype = tt
     F.fk_mailbox_wait.argtypes = [C.c_size_t, C.c_int]; F.fk_mailbox_wait.restype = C.c_int
+    F.enif_make_tuple_from_array.argtypes = [C.c_void_p, C.POINTER(tt), C.c_uint]
+    F.enif_make_tuple_from_array.restype = tt
     mods = {}
-    for mod, so in shims.items():
-        L = C.CDLL(so, mode=os.RTLD_LAZY)
-        L.nif_init.restype = C.POINTER(Entry)
-        mods[mod] = Module(F, L.nif_init())
-    _cache[outdir] = (F, mods)
+    _cache[outdir] = (F, mods)              # before load_shim, which asks for F
+    for mod, src in (("NativeTree", "exmc_native_tree_nif.c"), ("HipNative", "exmc_hip_nif.c")):
+        mods[mod] = load_shim(outdir, src)
     return _cache[outdir]
+
+
+def load_shim(outdir, src_name):
+    """c_src/<src_name> compiled against the declaration header and libexmc_hip.so, loaded beside the fake
+    runtime (built on first use): its Module. THE build line of a shim in the tests."""
+    F = build(outdir)[0]
+    so = os.path.join(outdir, "lib%s.so" % os.path.splitext(src_name)[0])
+    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared"] + _sanitize_flags() +
+                          ["-o", so, os.path.join(ROOT, "c_src", src_name), "-L" + LIBDIR, "-lexmc_hip",
+                           "-Wl,-rpath," + LIBDIR, "-Wl,-z,lazy", "-ldl"])
+    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    L.nif_init.restype = C.POINTER(Entry)
+    return Module(F, L.nif_init())
+
+
+def tuple_term(mod, *items):
+    """{a, b, ...} in the fake runtime (to_term converts Python tuples to lists)"""
+    arr = (C.c_ulong * max(len(items), 1))(*[mod.to_term(x) for x in items])
+    return _Term(mod.F.enif_make_tuple_from_array(None, arr, len(items)))
 
 
 class Module:

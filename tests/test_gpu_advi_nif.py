@@ -1,15 +1,11 @@
 """`Elixir.Exmc.NUTS.HipAdviNative.fit/12` (c_src/exmc_hip_advi_nif.c) called through
 tests/host/fake_erl_nif.c, as the BEAM would call it: equal to exmc_hip_advi_host bit for bit; a wrong
 tuple is a badarg; a kind without a compiled layout raises {:exmc_hip_error, 4, _}."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import nif_harness as H
-import test_gpu_ic_nif as IN
 from exmc_amd import advi, models, sampler
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +16,7 @@ KEYS = ("draws", "mu", "log_sigma", "elbo_history", "num_iters", "converged")
 
 @pytest.fixture(scope="module")
 def mod(tmp_path_factory):
-    outdir = str(tmp_path_factory.mktemp("advinif"))
-    F, _ = H.build(outdir)
-    so = os.path.join(outdir, "libHipAdviNative_nif.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so,
-                           os.path.join(H.ROOT, "c_src", "exmc_hip_advi_nif.c"), "-L" + H.LIBDIR, "-lexmc_hip",
-                           "-Wl,-rpath," + H.LIBDIR, "-Wl,-z,lazy", "-ldl"])
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
-    L.nif_init.restype = C.POINTER(H.Entry)
-    return H.Module(F, L.nif_init())
+    return H.load_shim(str(tmp_path_factory.mktemp("advinif")), "exmc_hip_advi_nif.c")
 
 
 @pytest.mark.parametrize("which", ["eight_schools", "sv"])
@@ -44,7 +32,7 @@ def test_fit_nif_equals_the_c_call(hip, mod, which):
     finally:
         comp.close()
     perm = [int(v) for v in spec.flat_order()]      # sv: the string sort, not the kernel order
-    got = mod.call("fit", IN.tuple_term(mod, spec.kind, spec.data), perm, 5, 2, 3, 15, 2, 9, lr, 0.02, 19, 0)
+    got = mod.call("fit", H.tuple_term(mod, spec.kind, spec.data), perm, 5, 2, 3, 15, 2, 9, lr, 0.02, 19, 0)
     assert isinstance(got, tuple) and len(got) == 6
     for b, k in zip(got, KEYS):
         assert b == np.ascontiguousarray(want[k]).tobytes(), k
@@ -52,11 +40,11 @@ def test_fit_nif_equals_the_c_call(hip, mod, which):
 
 def test_fit_nif_refusals(hip, mod):
     spec = models.eight_schools()
-    model = lambda: IN.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
+    model = lambda: H.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
     with pytest.raises(H.BadArg):                       # a list is not the {kind, data} tuple
         mod.call("fit", [spec.kind, spec.data], [], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 0)
     with pytest.raises(H.BadArg):                       # a 3-tuple neither
-        mod.call("fit", IN.tuple_term(mod, spec.kind, spec.data, 1), [], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 0)
+        mod.call("fit", H.tuple_term(mod, spec.kind, spec.data, 1), [], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 0)
     with pytest.raises(H.BadArg):                       # window_size below the bound
         mod.call("fit", model(), [], 2, 0, 3, 7, 1, 1, 0.01, 1e-4, 19, 0)
     with pytest.raises(H.BadArg):                       # no samples
@@ -64,7 +52,7 @@ def test_fit_nif_refusals(hip, mod):
     with pytest.raises(H.BadArg):                       # a flat order of the wrong length
         mod.call("fit", model(), [0, 1], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 0)
     with pytest.raises(H.Raised) as e:                  # a kind no layout row carries: {:exmc_hip_error, 4, _}
-        mod.call("fit", IN.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), [], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 0)
+        mod.call("fit", H.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), [], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 0)
     assert e.value.reason[:2] == (H.Atom("exmc_hip_error"), 4)
     with pytest.raises(H.Raised) as e:                  # a lane count that is not compiled in
         mod.call("fit", model(), [], 2, 0, 3, 7, 1, 4, 0.01, 1e-4, 19, 5)

@@ -2,8 +2,6 @@
 tests/host/fake_erl_nif.c, as the BEAM would call it: equal to exmc_hip_ic_stats_host bit for bit on
 draws in the layout HipNative's sampling functions return."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,29 +13,9 @@ from exmc_amd import model_comparison as MC
 pytestmark = pytest.mark.gpu
 
 
-def build_compare_shim(outdir):
-    F, _ = H.build(outdir)
-    so = os.path.join(outdir, "libHipCompareNative_nif.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so,
-                           os.path.join(H.ROOT, "c_src", "exmc_hip_compare_nif.c"), "-L" + H.LIBDIR, "-lexmc_hip",
-                           "-Wl,-rpath," + H.LIBDIR, "-Wl,-z,lazy", "-ldl"])
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
-    L.nif_init.restype = C.POINTER(H.Entry)
-    return H.Module(F, L.nif_init())
-
-
-def tuple_term(mod, *items):
-    """{a, b, ...} in the fake runtime (the harness converts Python tuples to lists)"""
-    F = mod.F
-    F.enif_make_tuple_from_array.argtypes = [C.c_void_p, C.POINTER(C.c_ulong), C.c_uint]
-    F.enif_make_tuple_from_array.restype = C.c_ulong
-    arr = (C.c_ulong * len(items))(*[mod.to_term(x) for x in items])
-    return H._Term(F.enif_make_tuple_from_array(None, arr, len(items)))
-
-
 @pytest.fixture(scope="module")
 def mod(tmp_path_factory):
-    return build_compare_shim(str(tmp_path_factory.mktemp("icnif")))
+    return H.load_shim(str(tmp_path_factory.mktemp("icnif")), "exmc_hip_compare_nif.c")
 
 
 def test_ic_stats_nif_equals_the_c_call(hip, mod):
@@ -46,16 +24,16 @@ def test_ic_stats_nif_equals_the_c_call(hip, mod):
     comp = sampler.compile(spec)
     _, stats = sampler.sample_chains_compiled(comp, 6, dict(num_warmup=80, num_samples=30, seed=3))
     draws = np.ascontiguousarray(stats[0]["extra"]["raw"]["draws"])       # [C][S][d], kernel order
-    got = H.f64(mod.call("ic_stats", tuple_term(mod, spec.kind, spec.data), draws, 6, 30)).reshape(4, 8)
+    got = H.f64(mod.call("ic_stats", H.tuple_term(mod, spec.kind, spec.data), draws, 6, 30)).reshape(4, 8)
     want = np.zeros((4, 8))
     comp.check(comp.L.exmc_hip_ic_stats_host(comp.h, draws.ctypes.data_as(C.POINTER(C.c_double)), 30, spec.d, 6,
                                              want.ctypes.data_as(C.POINTER(C.c_double))))
     assert got.tobytes() == want.tobytes()
     assert got.tobytes() == MC.pointwise_stats(comp, draws).tobytes()
     with pytest.raises(H.BadArg):
-        mod.call("ic_stats", tuple_term(mod, spec.kind, spec.data), draws[:, :, :5], 6, 30)
+        mod.call("ic_stats", H.tuple_term(mod, spec.kind, spec.data), draws[:, :, :5], 6, 30)
     with pytest.raises(H.BadArg):                       # a list is not the {kind, data} tuple
         mod.call("ic_stats", [spec.kind, spec.data], draws, 6, 30)
     with pytest.raises(H.Raised) as e:                  # a kind the library has no handle for: {:exmc_hip_error, 4, _}
-        mod.call("ic_stats", tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(6 * 30 * 2), 6, 30)
+        mod.call("ic_stats", H.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(6 * 30 * 2), 6, 30)
     assert e.value.reason[:2] == (H.Atom("exmc_hip_error"), 4)

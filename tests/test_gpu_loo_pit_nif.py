@@ -3,15 +3,12 @@ tests/host/fake_erl_nif.c, as the BEAM would call it: its table is its one funct
 exmc_hip_loo_pit_host byte for byte; a wrong tuple is a badarg; a kind without a handle raises
 {:exmc_hip_error, 4, _}."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import nif_harness as H
 import predictive_inputs as PI
-import test_gpu_ic_nif as IN
 from exmc_amd import _lib, models, sampler
 
 pytestmark = pytest.mark.gpu
@@ -21,15 +18,7 @@ ERL_NIF_DIRTY_JOB_IO_BOUND = 2
 
 @pytest.fixture(scope="module")
 def mod(tmp_path_factory):
-    outdir = str(tmp_path_factory.mktemp("loopitnif"))
-    F, _ = H.build(outdir)
-    so = os.path.join(outdir, "libHipLooPitNative_nif.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so,
-                           os.path.join(H.ROOT, "c_src", "exmc_hip_loo_pit_nif.c"), "-L" + H.LIBDIR, "-lexmc_hip",
-                           "-Wl,-rpath," + H.LIBDIR, "-Wl,-z,lazy", "-ldl"])
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
-    L.nif_init.restype = C.POINTER(H.Entry)
-    return H.Module(F, L.nif_init())
+    return H.load_shim(str(tmp_path_factory.mktemp("loopitnif")), "exmc_hip_loo_pit_nif.c")
 
 
 @pytest.mark.parametrize("kind", [models.EIGHT_SCHOOLS, models.SV])
@@ -48,7 +37,7 @@ def test_nif_equals_the_c_call(hip, mod, kind):
                                                 Cn, 0, out.ctypes.data_as(dp)))
     finally:
         comp.close()
-    got = mod.call("loo_pit", IN.tuple_term(mod, spec.kind, spec.data), draws, Cn, S, 19, 2)
+    got = mod.call("loo_pit", H.tuple_term(mod, spec.kind, spec.data), draws, Cn, S, 19, 2)
     assert got == out.tobytes()
     assert np.isfinite(out).all() and len(np.unique(out[2])) == N and ((out[2] > 0.0) & (out[2] < 1.0)).all()
 
@@ -56,11 +45,11 @@ def test_nif_equals_the_c_call(hip, mod, kind):
 def test_nif_refusals(hip, mod):
     spec = PI.spec(models.EIGHT_SCHOOLS)
     draws = np.zeros((2, 3, spec.d))
-    model = lambda: IN.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
+    model = lambda: H.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
     with pytest.raises(H.BadArg):                       # a list is not the {kind, data} tuple
         mod.call("loo_pit", [spec.kind, spec.data], draws, 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a 3-tuple neither
-        mod.call("loo_pit", IN.tuple_term(mod, spec.kind, spec.data, 1), draws, 2, 3, 19, 0)
+        mod.call("loo_pit", H.tuple_term(mod, spec.kind, spec.data, 1), draws, 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a trace of another size
         mod.call("loo_pit", model(), draws[:, :, :5], 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a negative chain_lo
@@ -70,5 +59,5 @@ def test_nif_refusals(hip, mod):
     with pytest.raises(H.BadArg):                       # one sample: the library's EXMC_ERR_BADARG is a badarg too
         mod.call("loo_pit", model(), np.zeros((1, 1, spec.d)), 1, 1, 19, 0)
     with pytest.raises(H.Raised) as e:                  # a kind the library has no handle for: {:exmc_hip_error, 4, _}
-        mod.call("loo_pit", IN.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(2 * 3 * 2), 2, 3, 19, 0)
+        mod.call("loo_pit", H.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(2 * 3 * 2), 2, 3, 19, 0)
     assert e.value.reason[:2] == (H.Atom("exmc_hip_error"), 4)

@@ -3,15 +3,12 @@ tests/host/fake_erl_nif.c, as the BEAM would call it: its table is its one funct
 exmc_hip_ppc_host byte for byte; a wrong tuple is a badarg; a kind without a handle raises
 {:exmc_hip_error, 4, _}."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import nif_harness as H
 import predictive_inputs as PI
-import test_gpu_ic_nif as IN
 from exmc_amd import _lib, models, sampler
 
 pytestmark = pytest.mark.gpu
@@ -21,15 +18,7 @@ ERL_NIF_DIRTY_JOB_IO_BOUND = 2
 
 @pytest.fixture(scope="module")
 def mod(tmp_path_factory):
-    outdir = str(tmp_path_factory.mktemp("ppcnif"))
-    F, _ = H.build(outdir)
-    so = os.path.join(outdir, "libHipPpcNative_nif.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so,
-                           os.path.join(H.ROOT, "c_src", "exmc_hip_ppc_nif.c"), "-L" + H.LIBDIR, "-lexmc_hip",
-                           "-Wl,-rpath," + H.LIBDIR, "-Wl,-z,lazy", "-ldl"])
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
-    L.nif_init.restype = C.POINTER(H.Entry)
-    return H.Module(F, L.nif_init())
+    return H.load_shim(str(tmp_path_factory.mktemp("ppcnif")), "exmc_hip_ppc_nif.c")
 
 
 @pytest.mark.parametrize("kind", [models.EIGHT_SCHOOLS, models.SV])
@@ -48,7 +37,7 @@ def test_nif_equals_the_c_call(hip, mod, kind):
                                             datum.ctypes.data_as(dp), t_obs.ctypes.data_as(dp), pv.ctypes.data_as(dp), None))
     finally:
         comp.close()
-    got = mod.call("ppc", IN.tuple_term(mod, spec.kind, spec.data), draws, Cn, S, 19, 2)
+    got = mod.call("ppc", H.tuple_term(mod, spec.kind, spec.data), draws, Cn, S, 19, 2)
     assert got == (datum.tobytes(), t_obs.tobytes(), pv.tobytes())
     assert np.isfinite(datum).all() and len(np.unique(datum[:, 0])) == N and (pv > 0.0).any()
 
@@ -56,11 +45,11 @@ def test_nif_equals_the_c_call(hip, mod, kind):
 def test_nif_refusals(hip, mod):
     spec = PI.spec(models.EIGHT_SCHOOLS)
     draws = np.zeros((2, 3, spec.d))
-    model = lambda: IN.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
+    model = lambda: H.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
     with pytest.raises(H.BadArg):                       # a list is not the {kind, data} tuple
         mod.call("ppc", [spec.kind, spec.data], draws, 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a 3-tuple neither
-        mod.call("ppc", IN.tuple_term(mod, spec.kind, spec.data, 1), draws, 2, 3, 19, 0)
+        mod.call("ppc", H.tuple_term(mod, spec.kind, spec.data, 1), draws, 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a trace of another size
         mod.call("ppc", model(), draws[:, :, :5], 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a negative chain_lo
@@ -68,5 +57,5 @@ def test_nif_refusals(hip, mod):
     with pytest.raises(H.BadArg):                       # no chains
         mod.call("ppc", model(), draws, 0, 3, 19, 0)
     with pytest.raises(H.Raised) as e:                  # a kind the library has no handle for: {:exmc_hip_error, 4, _}
-        mod.call("ppc", IN.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(2 * 3 * 2), 2, 3, 19, 0)
+        mod.call("ppc", H.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(2 * 3 * 2), 2, 3, 19, 0)
     assert e.value.reason[:2] == (H.Atom("exmc_hip_error"), 4)

@@ -2,15 +2,12 @@
 through tests/host/fake_erl_nif.c, as the BEAM would call it: equal to exmc_hip_posterior_predictive_host
 byte for byte; a wrong tuple is a badarg; a kind without a handle raises {:exmc_hip_error, 4, _}."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import nif_harness as H
 import predictive_inputs as PI
-import test_gpu_ic_nif as IN
 from exmc_amd import _lib, models, sampler
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +17,7 @@ ERL_NIF_DIRTY_JOB_IO_BOUND = 2
 
 @pytest.fixture(scope="module")
 def mod(tmp_path_factory):
-    outdir = str(tmp_path_factory.mktemp("ppnif"))
-    F, _ = H.build(outdir)
-    so = os.path.join(outdir, "libHipPredictiveNative_nif.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so,
-                           os.path.join(H.ROOT, "c_src", "exmc_hip_predictive_nif.c"), "-L" + H.LIBDIR, "-lexmc_hip",
-                           "-Wl,-rpath," + H.LIBDIR, "-Wl,-z,lazy", "-ldl"])
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
-    L.nif_init.restype = C.POINTER(H.Entry)
-    return H.Module(F, L.nif_init())
+    return H.load_shim(str(tmp_path_factory.mktemp("predictivenif")), "exmc_hip_predictive_nif.c")
 
 
 @pytest.mark.parametrize("kind", [models.EIGHT_SCHOOLS, models.SV])
@@ -47,7 +36,7 @@ def test_nif_equals_the_c_call(hip, mod, kind):
                                                              S, spec.d, Cn, None, want.ctypes.data_as(dp)))
     finally:
         comp.close()
-    got = mod.call("posterior_predictive", IN.tuple_term(mod, spec.kind, spec.data), draws, Cn, S, 19, 2)
+    got = mod.call("posterior_predictive", H.tuple_term(mod, spec.kind, spec.data), draws, Cn, S, 19, 2)
     assert got == want.tobytes()
     assert np.isfinite(want).all() and len(np.unique(want)) > Cn * S
 
@@ -55,11 +44,11 @@ def test_nif_equals_the_c_call(hip, mod, kind):
 def test_nif_refusals(hip, mod):
     spec = PI.spec(models.EIGHT_SCHOOLS)
     draws = np.zeros((2, 3, spec.d))
-    model = lambda: IN.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
+    model = lambda: H.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
     with pytest.raises(H.BadArg):                       # a list is not the {kind, data} tuple
         mod.call("posterior_predictive", [spec.kind, spec.data], draws, 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a 3-tuple neither
-        mod.call("posterior_predictive", IN.tuple_term(mod, spec.kind, spec.data, 1), draws, 2, 3, 19, 0)
+        mod.call("posterior_predictive", H.tuple_term(mod, spec.kind, spec.data, 1), draws, 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a trace of another size
         mod.call("posterior_predictive", model(), draws[:, :, :5], 2, 3, 19, 0)
     with pytest.raises(H.BadArg):                       # a negative chain_lo
@@ -67,5 +56,5 @@ def test_nif_refusals(hip, mod):
     with pytest.raises(H.BadArg):                       # no chains
         mod.call("posterior_predictive", model(), draws, 0, 3, 19, 0)
     with pytest.raises(H.Raised) as e:                  # a kind the library has no handle for: {:exmc_hip_error, 4, _}
-        mod.call("posterior_predictive", IN.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(2 * 3 * 2), 2, 3, 19, 0)
+        mod.call("posterior_predictive", H.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), np.zeros(2 * 3 * 2), 2, 3, 19, 0)
     assert e.value.reason[:2] == (H.Atom("exmc_hip_error"), 4)

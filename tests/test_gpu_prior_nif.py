@@ -2,15 +2,12 @@
 tests/host/fake_erl_nif.c, as the BEAM would call it: equal to exmc_hip_prior_samples_host byte for byte, with
 and without replicates; a wrong tuple is a badarg; a kind without a handle raises {:exmc_hip_error, 4, _}."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import nif_harness as H
 import predictive_inputs as PI
-import test_gpu_ic_nif as IN
 from exmc_amd import _lib, models, sampler
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +17,7 @@ ERL_NIF_DIRTY_JOB_IO_BOUND = 2
 
 @pytest.fixture(scope="module")
 def mod(tmp_path_factory):
-    outdir = str(tmp_path_factory.mktemp("priornif"))
-    F, _ = H.build(outdir)
-    so = os.path.join(outdir, "libHipPriorNative_nif.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-o", so,
-                           os.path.join(H.ROOT, "c_src", "exmc_hip_prior_nif.c"), "-L" + H.LIBDIR, "-lexmc_hip",
-                           "-Wl,-rpath," + H.LIBDIR, "-Wl,-z,lazy", "-ldl"])
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
-    L.nif_init.restype = C.POINTER(H.Entry)
-    return H.Module(F, L.nif_init())
+    return H.load_shim(str(tmp_path_factory.mktemp("priornif")), "exmc_hip_prior_nif.c")
 
 
 @pytest.mark.parametrize("kind", [models.EIGHT_SCHOOLS, models.SV_NCP])
@@ -52,11 +41,11 @@ def test_nif_equals_the_c_call(hip, mod, kind):
                                                  bq.ctypes.data_as(dp), None), L)
     finally:
         L.exmc_hip_model_destroy(h)
-    got = mod.call("prior_samples", IN.tuple_term(mod, spec.kind, spec.data), Cn, S, 19, 2, 1)
+    got = mod.call("prior_samples", H.tuple_term(mod, spec.kind, spec.data), Cn, S, 19, 2, 1)
     assert isinstance(got, tuple) and len(got) == 3
     assert got[0] == wx.tobytes() and got[1] == wq.tobytes() and got[2] == wy.tobytes()
     assert np.isfinite(wx).all() and np.isfinite(wy).all() and len(np.unique(wy)) > Cn * S
-    bare = mod.call("prior_samples", IN.tuple_term(mod, spec.kind, spec.data), Cn, S, 19, 2, 0)
+    bare = mod.call("prior_samples", H.tuple_term(mod, spec.kind, spec.data), Cn, S, 19, 2, 0)
     assert bare[0] == bx.tobytes() and bare[1] == bq.tobytes() and bare[2] == b""
     assert bx[:, 0].tobytes() == wx[:, 0].tobytes() and bx[:, 1].tobytes() != wx[:, 1].tobytes()
     # for a kind whose handle sampler.compile makes with the same flat order, the compiled handle agrees
@@ -72,11 +61,11 @@ def test_nif_equals_the_c_call(hip, mod, kind):
 
 def test_nif_refusals(hip, mod):
     spec = PI.spec(models.EIGHT_SCHOOLS)
-    model = lambda: IN.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
+    model = lambda: H.tuple_term(mod, spec.kind, spec.data)   # noqa: E731
     with pytest.raises(H.BadArg):                       # a list is not the {kind, data} tuple
         mod.call("prior_samples", [spec.kind, spec.data], 2, 3, 19, 0, 1)
     with pytest.raises(H.BadArg):                       # a 3-tuple neither
-        mod.call("prior_samples", IN.tuple_term(mod, spec.kind, spec.data, 1), 2, 3, 19, 0, 1)
+        mod.call("prior_samples", H.tuple_term(mod, spec.kind, spec.data, 1), 2, 3, 19, 0, 1)
     with pytest.raises(H.BadArg):                       # a negative chain_lo
         mod.call("prior_samples", model(), 2, 3, 19, -1, 1)
     with pytest.raises(H.BadArg):                       # no chains, no draws
@@ -86,5 +75,5 @@ def test_nif_refusals(hip, mod):
     with pytest.raises(H.BadArg):                       # replicates is 0 or 1
         mod.call("prior_samples", model(), 2, 3, 19, 0, 2)
     with pytest.raises(H.Raised) as e:                  # a kind the library has no handle for: {:exmc_hip_error, 4, _}
-        mod.call("prior_samples", IN.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), 2, 3, 19, 0, 1)
+        mod.call("prior_samples", H.tuple_term(mod, models.STD_NORMAL, np.zeros(0)), 2, 3, 19, 0, 1)
     assert e.value.reason[:2] == (H.Atom("exmc_hip_error"), 4)

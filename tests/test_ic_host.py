@@ -229,21 +229,3 @@ def test_radon_spec_maps_datums_back_to_the_callers_order():
     order = spec.datum_order
     assert sorted(order) == list(range(N))
     np.testing.assert_array_equal(spec.data[171 + N:], y[order])
-
-
-def test_compare_nif_table_equals_its_elixir_stubs():
-    """c_src/exmc_hip_compare_nif.c's ErlNifFunc table against elixir/.../hip_compare_native.ex"""
-    c = open(os.path.join(ROOT, "c_src", "exmc_hip_compare_nif.c")).read()
-    table = dict((n, int(a)) for n, a in re.findall(r'\{"(\w+)", (\d+), \w+, ERL_NIF_DIRTY_JOB_IO_BOUND\}', c))
-    ex = open(os.path.join(ROOT, "elixir", "lib", "exmc", "nuts", "hip_compare_native.ex")).read()
-    stubs = {n: len([a for a in args.split(",") if a.strip()])
-             for n, args in re.findall(r"def (\w+)\(([^)]*)\), do: :erlang.nif_error", ex)}
-    assert table == stubs == {"ic_stats": 4}
-    assert "ERL_NIF_INIT(Elixir.Exmc.NUTS.HipCompareNative," in c
-    sampler_src = open(os.path.join(ROOT, "elixir", "lib", "exmc", "nuts", "hip_sampler.ex")).read()
-    assert "HipCompareNative.ic_stats(model, draws," in sampler_src
-
-
-def test_compare_nif_compiles_against_the_declarations(tmp_path):
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-c", "-o",
-                           str(tmp_path / "nif.o"), os.path.join(ROOT, "c_src", "exmc_hip_compare_nif.c")])

@@ -1,10 +1,8 @@
 """The statement of the posterior predictive checks (tests/ppc_statement.py) on the CPU, on the replicates
 tests/predictive_inputs.py already provides: its counts are numpy's own comparisons; its moments agree
 with numpy's within rounding; p-values and PIT values are probabilities; a batch sharded at a multiple of
-64 chains equals the whole; on data drawn from the model the check is calibrated (no extreme value). And
-the BEAM side as source files: the NIF table names what the Elixir stub names."""
-import os
-import re
+64 chains equals the whole; on data drawn from the model the check is calibrated (no extreme value). (The
+BEAM side as source files: tests/test_beam_boundary_sources.py.)"""
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ import pytest
 import ppc_statement as PPC
 import predictive_inputs as PI
 import predictive_statement as PS
-import test_elixir_sources as ES
 from exmc_amd import models
 
 U = 2.0 ** -53      # the unit roundoff of float64
@@ -132,48 +129,3 @@ def test_calibration_on_data_drawn_from_the_model():
     r = PPC.run(yrep, PPC.observed(models.SIMPLE, spec.data))
     assert ((r["pit"] > 0.0) & (r["pit"] < 1.0)).all(), r["pit"]
     assert ((r["p_value"] > 0.0) & (r["p_value"] < 1.0)).all(), r["p_value"]
-
-
-# ---- the BEAM side as source files -----------------------------------------------------------------
-C_SRC = os.path.join(ES.ROOT, "c_src", "exmc_hip_ppc_nif.c")
-
-
-def test_nif_table_equals_the_elixir_stub():
-    c = open(C_SRC).read()
-    rows = re.findall(r'\{"(\w+)", (\d+), (\w+), (\w+)\}', c[c.index("static ErlNifFunc nif_funcs[]"):])
-    assert rows == [("ppc", "6", "ppc", "ERL_NIF_DIRTY_JOB_IO_BOUND")]
-    assert "ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPpcNative," in c
-    ex = ES._read(ES.EX, "lib", "exmc", "nuts", "hip_ppc_native.ex")
-    assert "defmodule Exmc.NUTS.HipPpcNative do" in ex and "@on_load :load_nif" in ex
-    assert ":erlang.load_nif" in ex and "exmc_hip_ppc_nif" in ex
-    stubs = {m.group(1): len(ES._split_args(m.group(2))) for m in re.finditer(
-        r"def\s+([a-z_]+)\(([^)]*)\)\s*,?\s*do:\s*:erlang\.nif_error\(:nif_not_loaded\)", ES._strip(ex))}
-    assert stubs == {"ppc": 6}
-
-
-def test_wrapper_calls_the_stub_with_its_arity():
-    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", "hip_ppc.ex"))
-    m = re.search(r"HipPpcNative\.ppc\(", src)
-    i, depth = m.end(), 1
-    while depth:
-        depth += {"(": 1, ")": -1}.get(src[i], 0)
-        i += 1
-    assert len(ES._split_args(src[m.end():i - 1])) == 6
-    assert "def ppc(" in src
-
-
-@pytest.mark.parametrize("name", ["hip_ppc_native.ex", "hip_ppc.ex"])
-def test_blocks_balance(name):
-    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", name))
-    opens = len(re.findall(r"\bdo\b(?!:)", src)) + len(re.findall(r"\bfn\b", src))
-    assert opens == len(re.findall(r"\bend\b", src)), name
-    for a, b in ("()", "[]", "{}"):
-        assert src.count(a) == src.count(b), (name, a)
-    assert src.lstrip().startswith("defmodule Exmc.NUTS.")
-
-
-def test_shim_compiles_against_the_declaration_header(tmp_path):
-    import subprocess
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-c", "-o",
-                           str(tmp_path / "nif.o"), C_SRC])
-    assert "exmc_hip_ppc_nif" in open(os.path.join(ES.ROOT, "INTEGRATION.md")).read()

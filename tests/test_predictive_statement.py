@@ -1,17 +1,14 @@
 """The statement of posterior predictive sampling (tests/predictive_statement.py) on the CPU: its samplers
 draw from the distributions they name; the inputs of the GPU parity test take every branch of the
-samplers and never reach the gamma cap; hostile traces terminate; the NIF table names what the Elixir
-stub names."""
+samplers and never reach the gamma cap; hostile traces terminate. (The NIF table against the Elixir
+stub: tests/test_beam_boundary_sources.py.)"""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 import predictive_inputs as PI
 import predictive_statement as PS
-import test_elixir_sources as ES
 from exmc_amd import models
 
 N_MOMENTS = 20000
@@ -145,48 +142,3 @@ def test_continuation_of_the_statement():
     a, sa, _ = PS.run(kind, blob, x[:1], seed=5, chain_lo=1)
     b, sb, _ = PS.run(kind, blob, x[1:], states=sa)
     assert np.concatenate([a, b]).tobytes() == whole.tobytes() and sb.tobytes() == st.tobytes()
-
-
-# ---- the BEAM side as source files -----------------------------------------------------------------
-C_SRC = os.path.join(ES.ROOT, "c_src", "exmc_hip_predictive_nif.c")
-
-
-def test_nif_table_equals_the_elixir_stub():
-    c = open(C_SRC).read()
-    rows = re.findall(r'\{"(\w+)", (\d+), (\w+), (\w+)\}', c[c.index("static ErlNifFunc nif_funcs[]"):])
-    assert rows == [("posterior_predictive", "6", "posterior_predictive", "ERL_NIF_DIRTY_JOB_IO_BOUND")]
-    assert "ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPredictiveNative," in c
-    ex = ES._read(ES.EX, "lib", "exmc", "nuts", "hip_predictive_native.ex")
-    assert "defmodule Exmc.NUTS.HipPredictiveNative do" in ex and "@on_load :load_nif" in ex
-    assert ":erlang.load_nif" in ex and "exmc_hip_predictive_nif" in ex
-    stubs = {m.group(1): len(ES._split_args(m.group(2))) for m in re.finditer(
-        r"def\s+([a-z_]+)\(([^)]*)\)\s*,?\s*do:\s*:erlang\.nif_error\(:nif_not_loaded\)", ES._strip(ex))}
-    assert stubs == {"posterior_predictive": 6}
-
-
-def test_wrapper_calls_the_stub_with_its_arity():
-    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", "hip_predictive.ex"))
-    m = re.search(r"HipPredictiveNative\.posterior_predictive\(", src)
-    i, depth = m.end(), 1
-    while depth:
-        depth += {"(": 1, ")": -1}.get(src[i], 0)
-        i += 1
-    assert len(ES._split_args(src[m.end():i - 1])) == 6
-    assert "def posterior_predictive(" in src
-
-
-@pytest.mark.parametrize("name", ["hip_predictive_native.ex", "hip_predictive.ex"])
-def test_blocks_balance(name):
-    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", name))
-    opens = len(re.findall(r"\bdo\b(?!:)", src)) + len(re.findall(r"\bfn\b", src))
-    assert opens == len(re.findall(r"\bend\b", src)), name
-    for a, b in ("()", "[]", "{}"):
-        assert src.count(a) == src.count(b), (name, a)
-    assert src.lstrip().startswith("defmodule Exmc.NUTS.")
-
-
-def test_shim_compiles_against_the_declaration_header(tmp_path):
-    import subprocess
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-c", "-o",
-                           str(tmp_path / "nif.o"), C_SRC])
-    assert "exmc_hip_predictive_nif" in open(os.path.join(ES.ROOT, "INTEGRATION.md")).read()

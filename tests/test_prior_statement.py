@@ -1,10 +1,8 @@
 """The statement of prior sampling (tests/prior_statement.py) on the CPU: the Kahn order of every kind, sv and
 sv_ncp pinned literally; HalfCauchy and Exponential draw from the laws they name, and the sv walk's increments
 are standard normal; a generator that holds 0.0 gives the stated values and goes on; the inputs of the GPU
-parity tests never reach the gamma cap; the BEAM side as source files."""
+parity tests never reach the gamma cap. (The BEAM side as source files: tests/test_beam_boundary_sources.py.)"""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ import pytest
 import predictive_inputs as PI
 import predictive_statement as PS
 import prior_statement as PR
-import test_elixir_sources as ES
 from exmc_amd import models
 
 N_DRAWS = 20000
@@ -152,48 +149,3 @@ def test_continuation_and_no_replicates():
     bare = PR.run(sp, 2, 3, seed=5, chain_lo=1, replicates=False)
     assert bare[2] is None and bare[0][0].tobytes() == a[0][0].tobytes()
     assert bare[0][1].tobytes() != a[0][1].tobytes()          # the generator did not advance for the datums
-
-
-# ---- the BEAM side as source files -----------------------------------------------------------------
-C_SRC = os.path.join(ES.ROOT, "c_src", "exmc_hip_prior_nif.c")
-
-
-def test_nif_table_equals_the_elixir_stub():
-    c = open(C_SRC).read()
-    rows = re.findall(r'\{"(\w+)", (\d+), (\w+), (\w+)\}', c[c.index("static ErlNifFunc nif_funcs[]"):])
-    assert rows == [("prior_samples", "6", "prior_samples", "ERL_NIF_DIRTY_JOB_IO_BOUND")]
-    assert "ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPriorNative," in c
-    ex = ES._read(ES.EX, "lib", "exmc", "nuts", "hip_prior_native.ex")
-    assert "defmodule Exmc.NUTS.HipPriorNative do" in ex and "@on_load :load_nif" in ex
-    assert ":erlang.load_nif" in ex and "exmc_hip_prior_nif" in ex
-    stubs = {m.group(1): len(ES._split_args(m.group(2))) for m in re.finditer(
-        r"def\s+([a-z_]+)\(([^)]*)\)\s*,?\s*do:\s*:erlang\.nif_error\(:nif_not_loaded\)", ES._strip(ex))}
-    assert stubs == {"prior_samples": 6}
-
-
-def test_wrapper_calls_the_stub_with_its_arity():
-    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", "hip_prior.ex"))
-    m = re.search(r"HipPriorNative\.prior_samples\(", src)
-    i, depth = m.end(), 1
-    while depth:
-        depth += {"(": 1, ")": -1}.get(src[i], 0)
-        i += 1
-    assert len(ES._split_args(src[m.end():i - 1])) == 6
-    assert "def prior_samples(" in src
-
-
-@pytest.mark.parametrize("name", ["hip_prior_native.ex", "hip_prior.ex"])
-def test_blocks_balance(name):
-    src = ES._strip(ES._read(ES.EX, "lib", "exmc", "nuts", name))
-    opens = len(re.findall(r"\bdo\b(?!:)", src)) + len(re.findall(r"\bfn\b", src))
-    assert opens == len(re.findall(r"\bend\b", src)), name
-    for a, b in ("()", "[]", "{}"):
-        assert src.count(a) == src.count(b), (name, a)
-    assert src.lstrip().startswith("defmodule Exmc.NUTS.")
-
-
-def test_shim_compiles_against_the_declaration_header(tmp_path):
-    import subprocess
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-c", "-o",
-                           str(tmp_path / "nif.o"), C_SRC])
-    assert "exmc_hip_prior_nif" in open(os.path.join(ES.ROOT, "INTEGRATION.md")).read()

@@ -40,22 +40,6 @@ def test_every_handle_entry_point_is_held_to_the_handle_state_rules():
     assert all("L.%s(" % n in op for n in handle)
 
 
-def test_psis_nif_table_equals_its_elixir_stub_and_compiles(tmp_path):
-    """c_src/exmc_hip_psis_nif.c's ErlNifFunc table against elixir/.../hip_psis_native.ex, and the sampler's call"""
-    path = os.path.join(ROOT, "c_src", "exmc_hip_psis_nif.c")
-    c = open(path).read()
-    table = dict((n, int(a)) for n, a in re.findall(r'\{"(\w+)", (\d+), \w+, ERL_NIF_DIRTY_JOB_IO_BOUND\}', c))
-    ex = open(os.path.join(ROOT, "elixir", "lib", "exmc", "nuts", "hip_psis_native.ex")).read()
-    stubs = {n: len([a for a in args.split(",") if a.strip()])
-             for n, args in re.findall(r"def (\w+)\(([^)]*)\), do: :erlang.nif_error", ex)}
-    assert table == stubs == {"psis_stats": 4}
-    assert "ERL_NIF_INIT(Elixir.Exmc.NUTS.HipPsisNative," in c and "defmodule Exmc.NUTS.HipPsisNative do" in ex
-    sampler_src = open(os.path.join(ROOT, "elixir", "lib", "exmc", "nuts", "hip_sampler.ex")).read()
-    assert "Exmc.NUTS.HipPsisNative.psis_stats(model, draws," in sampler_src and "def psis_loo(" in sampler_src
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-fPIC", "-c", "-o",
-                           str(tmp_path / "nif.o"), path])
-
-
 def test_k_threshold():
     assert MC.k_threshold(100) == 0.5 and MC.k_threshold(10 ** 6) == 0.7
     assert abs(MC.k_threshold(2200) - 0.7) < 1e-3 and MC.k_threshold(2000) < 0.7
