@@ -48,6 +48,10 @@ PF_MAX_HISTORY = 6
 # include/exmc_hip_advi.h: Exmc.ADVI, one mean-field fit per lane group
 ADVI_EXPORTS = ["exmc_hip_advi", "exmc_hip_advi_host"]
 
+# include/exmc_hip_smc.h: Exmc.SMC, one particle per lane group
+SMC_EXPORTS = ["exmc_hip_smc_init", "exmc_hip_smc_mutate", "exmc_hip_smc_reweight", "exmc_hip_smc", "exmc_hip_smc_host"]
+SMC_DEFAULT_MAX_STAGES = 1000
+
 # include/exmc_hip_fit_psis.h: the Pareto-smoothed importance ratios of the fits' draws and their resampling
 FIT_PSIS_EXPORTS = ["exmc_hip_fit_log_ratio", "exmc_hip_ratio_psis_from_lr", "exmc_hip_ratio_gather",
                     "exmc_hip_fit_psis", "exmc_hip_fit_psis_host"]
@@ -90,6 +94,17 @@ class Tuning(C.Structure):
 class PfOpts(C.Structure):
     _fields_ = [("num_draws", C.c_int), ("max_iters", C.c_int), ("history_size", C.c_int),
                 ("seed", C.c_uint64), ("lanes_per_chain", C.c_int)]
+
+
+class SmcOpts(C.Structure):
+    _fields_ = [("num_particles", C.c_int), ("threshold_ratio", C.c_double), ("num_mh_steps", C.c_int),
+                ("seed", C.c_uint64), ("max_stages", C.c_int), ("lanes_per_chain", C.c_int)]
+
+
+class SmcState(C.Structure):
+    """exmc_hip_smc_state: device pointers"""
+    _fields_ = [(k, C.c_void_p) for k in ("beta", "run_rng", "active", "scale", "accept", "betas", "ess_history",
+                                          "acceptance_rates", "num_stages", "status", "active_count")]
 
 
 class AdviOpts(C.Structure):
@@ -206,6 +221,11 @@ def bind(path):
     L.exmc_hip_pathfinder_host.argtypes = [vp, PfOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip, ip]
     L.exmc_hip_advi.argtypes = [vp, AdviOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.exmc_hip_advi_host.argtypes = [vp, AdviOpts, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
+    L.exmc_hip_smc_init.argtypes = [vp, SmcOpts, C.c_int, C.c_int, vp, vp, vp, SmcState]
+    L.exmc_hip_smc_mutate.argtypes = [vp, SmcOpts, C.c_int, vp, vp, vp, SmcState]
+    L.exmc_hip_smc_reweight.argtypes = [C.c_int, SmcOpts, C.c_int, C.c_int, C.c_int, vp, vp, SmcState]
+    L.exmc_hip_smc.argtypes = [vp, SmcOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.exmc_hip_smc_host.argtypes = [vp, SmcOpts, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, ip]
     L.exmc_hip_fit_log_ratio.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.exmc_hip_ratio_psis_from_lr.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp, vp]
     L.exmc_hip_ratio_gather.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]

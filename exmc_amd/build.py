@@ -30,6 +30,7 @@ DEPS = [
     os.path.join(HERE, "csrc", "exmc_gen_pointwise.hpp"),
     os.path.join(HERE, "csrc", "exmc_pathfinder.hpp"),
     os.path.join(HERE, "csrc", "exmc_advi.hpp"),
+    os.path.join(HERE, "csrc", "exmc_smc.hpp"),
     os.path.join(HERE, "csrc", "exmc_fit_psis.hpp"),
     os.path.join(HERE, "csrc", "exmc_psis_ratio.hpp"),
     os.path.join(HERE, "csrc", "exmc_predictive.hpp"),
@@ -46,6 +47,7 @@ DEPS = [
     os.path.join(ROOT, "include", "exmc_hip_pointwise.h"),
     os.path.join(ROOT, "include", "exmc_hip_pathfinder.h"),
     os.path.join(ROOT, "include", "exmc_hip_advi.h"),
+    os.path.join(ROOT, "include", "exmc_hip_smc.h"),
     os.path.join(ROOT, "include", "exmc_hip_fit_psis.h"),
     os.path.join(ROOT, "include", "exmc_hip_predictive.h"),
     os.path.join(ROOT, "include", "exmc_hip_ppc.h"),

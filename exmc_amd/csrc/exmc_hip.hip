@@ -11,6 +11,7 @@
 #include "../../include/exmc_hip_compare.h"
 #include "../../include/exmc_hip_pathfinder.h"
 #include "../../include/exmc_hip_advi.h"
+#include "../../include/exmc_hip_smc.h"
 #include "../../include/exmc_hip_fit_psis.h"
 #include "../../include/exmc_hip_predictive.h"
 #include "../../include/exmc_hip_ppc.h"
@@ -2849,6 +2850,305 @@ int exmc_hip_advi_host(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int 
 
 }  // extern "C"
 
+// ---- SMC (include/exmc_hip_smc.h; exmc_smc.hpp) --------------------------------------------------------
+namespace {
+
+int smc_max_stages(const exmc_hip_smc_opts& o) { return o.max_stages > 0 ? o.max_stages : EXMC_SMC_DEFAULT_MAX_STAGES; }
+
+int smc_opts_check(const exmc_hip_smc_opts& o, int n_runs, int run_lo) {
+  if (o.num_particles < 1 || o.num_mh_steps < 1 || !std::isfinite(o.threshold_ratio) || o.max_stages < 0)
+    return fail(EXMC_ERR_BADARG, "smc: num_particles >= 1, num_mh_steps >= 1, threshold_ratio finite and max_stages >= 0");
+  if (n_runs < 1 || run_lo < 0 || (long long)n_runs * o.num_particles > 0x7FFFFFFFLL)
+    return fail(EXMC_ERR_BADARG, "smc: bad arguments");
+  return EXMC_OK;
+}
+
+int smc_state_check(const exmc_hip_smc_state& s, const void* q, const void* logp) {
+  if (!q || !logp || !s.beta || !s.run_rng || !s.active || !s.scale || !s.accept || !s.betas || !s.ess_history ||
+      !s.acceptance_rates || !s.num_stages || !s.status || !s.active_count)
+    return fail(EXMC_ERR_BADARG, "smc: the arrays of the state are all required");
+  return EXMC_OK;
+}
+
+SmcRuns smc_runs(const exmc_hip_smc_state& s) {
+  return SmcRuns{s.beta, s.run_rng, s.active, s.scale, s.accept, s.betas, s.ess_history, s.acceptance_rates,
+                 s.num_stages, s.status, s.active_count};
+}
+
+SmcParams smc_params(exmc_hip_model* m, const exmc_hip_smc_opts& o, int n_runs, int run_lo, double* q, double* logp,
+                     uint64_t* words, const exmc_hip_smc_state& st) {
+  SmcParams P;
+  P.n_chains = n_runs * o.num_particles;
+  P.n_particles = o.num_particles;
+  P.n_runs = n_runs;
+  P.run_lo = run_lo;
+  P.base_seed = o.seed;
+  P.num_mh_steps = o.num_mh_steps;
+  P.max_stages = smc_max_stages(o);
+  P.q = q;
+  P.logp = logp;
+  P.words = words;
+  P.runs = smc_runs(st);
+  P.rng = rng_args(m);
+  P.flat = flat_order(m);
+  return P;
+}
+
+// smc_init_kernel or smc_mutate_kernel of the handle's layout on its stream; the caller records the events
+template <bool kInit>
+int smc_model_launch(exmc_hip_model* m, int lanes, const SmcParams& P) {
+  return dispatch(m, lanes, [&](auto tag, const auto& mc) {
+    using T = decltype(tag);
+    const size_t xlds = aux_lds_bytes<typename T::M>();
+    if constexpr (kInit) {
+      EXMC_KLAUNCH(m->device, (smc_init_kernel<typename T::M, T::G>), grid_for(P.n_chains, T::G, kBlock), dim3(kBlock),
+                   xlds, m->stream, P, mc);
+    } else {
+      EXMC_KLAUNCH(m->device, (smc_mutate_kernel<typename T::M, T::G>), grid_for(P.n_chains, T::G, kBlock), dim3(kBlock),
+                   xlds, m->stream, P, mc);
+    }
+    HIP_TRY(hipGetLastError());
+    return (int)EXMC_OK;
+  });
+}
+
+#ifndef EXMC_ONLY_CUSTOM
+// the scratch of the model-free front of a stage, one allocation
+struct SmcScratch {
+  CallBuf buf;
+  int n_blocks = 0;
+  double *nw = nullptr, *rcum = nullptr, *tot = nullptr, *base = nullptr, *q2 = nullptr, *lp2 = nullptr;
+  int32_t *resample = nullptr, *idx = nullptr;
+  int alloc(int N, int R, int d) {
+    const size_t C = (size_t)N * R;
+    n_blocks = (N + kRatioScan - 1) / kRatioScan;
+    const size_t n_tot = (size_t)n_blocks * R, n_base = ((size_t)n_blocks + 1) * R;
+    const size_t doubles = C + C + n_tot + n_base + (size_t)d * C + C;
+    int rc = buf.alloc(doubles * 8 + ((size_t)R + C) * 4);
+    if (rc) return rc;
+    nw = buf.as<double>();
+    rcum = nw + C;
+    tot = rcum + C;
+    base = tot + n_tot;
+    q2 = base + n_base;
+    lp2 = q2 + (size_t)d * C;
+    resample = (int32_t*)(lp2 + C);
+    idx = resample + R;
+    return EXMC_OK;
+  }
+};
+
+// exmc_hip_smc_reweight's launches for one stage
+int smc_stage_launch(hipStream_t stream, const SmcScratch& sc, const exmc_hip_smc_opts& o, int n_runs, int d, int stage,
+                     double* q, double* logp, const SmcRuns& runs) {
+  const int N = o.num_particles, R = n_runs, max_stages = smc_max_stages(o);
+  const long long C = (long long)N * R;
+  const SmcStage S{N, R, stage, max_stages, o.num_mh_steps, o.threshold_ratio * (double)N, d, std::sqrt((double)d), runs};
+  hipLaunchKernelGGL(smc_close_kernel, dim3(1), dim3(kSmcBlock), 0, stream, S);
+  HIP_TRY(hipGetLastError());
+  if (stage >= max_stages) return EXMC_OK;
+  if (N <= kSmcLdsParticles)
+    hipLaunchKernelGGL(smc_weights_kernel<true>, dim3((unsigned)R), dim3(kSmcBlock), (size_t)N * 8, stream, S, logp, sc.nw,
+                       sc.resample);
+  else
+    hipLaunchKernelGGL(smc_weights_kernel<false>, dim3((unsigned)R), dim3(kSmcBlock), 0, stream, S, logp, sc.nw,
+                       sc.resample);
+  HIP_TRY(hipGetLastError());
+  const long long lanes = (long long)R * sc.n_blocks;
+  hipLaunchKernelGGL(ratio_scan_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, sc.nw, 1, R, N,
+                     sc.n_blocks, 1, sc.rcum, sc.tot);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(smc_resample_kernel, dim3((unsigned)R), dim3(kSmcBlock), 0, stream, S, sc.rcum, sc.tot, sc.base,
+                     sc.n_blocks, sc.resample, sc.idx);
+  HIP_TRY(hipGetLastError());
+  const long long total = ((long long)d + 1) * C;
+  hipLaunchKernelGGL(smc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, q, logp, sc.idx, d,
+                     N, C, sc.q2, sc.lp2);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(q, sc.q2, (size_t)d * C * 8, hipMemcpyDeviceToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(logp, sc.lp2, (size_t)C * 8, hipMemcpyDeviceToDevice, stream));
+  hipLaunchKernelGGL(smc_scale_kernel, dim3((unsigned)R, (unsigned)d), dim3(kSmcBlock), 0, stream, S, q, C);
+  HIP_TRY(hipGetLastError());
+  return EXMC_OK;
+}
+#endif
+
+}  // namespace
+
+extern "C" {
+
+int exmc_hip_smc_init(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* q_dev,
+                      double* logp_dev, uint64_t* rng_words_dev, exmc_hip_smc_state st) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  int rc = smc_opts_check(o, n_runs, run_lo);
+  if (!rc) rc = smc_state_check(st, q_dev, logp_dev);
+  if (!rc && !rng_words_dev) rc = fail(EXMC_ERR_BADARG, "smc: the arrays of the state are all required");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const SmcParams P = smc_params(m, o, n_runs, run_lo, q_dev, logp_dev, rng_words_dev, st);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  rc = smc_model_launch<true>(m, resolve_lanes(m, o.lanes_per_chain), P);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the launch
+}
+
+int exmc_hip_smc_mutate(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, double* q_dev, double* logp_dev,
+                        uint64_t* rng_words_dev, exmc_hip_smc_state st) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  int rc = smc_opts_check(o, n_runs, 0);
+  if (!rc) rc = smc_state_check(st, q_dev, logp_dev);
+  if (!rc && !rng_words_dev) rc = fail(EXMC_ERR_BADARG, "smc: the arrays of the state are all required");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  const SmcParams P = smc_params(m, o, n_runs, 0, q_dev, logp_dev, rng_words_dev, st);
+  HIP_TRY(hipEventRecord(m->ev0, m->stream));
+  rc = smc_model_launch<false>(m, resolve_lanes(m, o.lanes_per_chain), P);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(m->ev1, m->stream));
+  return finish_timing(m);   // waits for the launch
+}
+
+int exmc_hip_smc_reweight(int device, exmc_hip_smc_opts o, int n_runs, int d, int stage, double* q_dev,
+                          double* logp_dev, exmc_hip_smc_state st) {
+  int rc = smc_opts_check(o, n_runs, 0);
+  if (!rc) rc = smc_state_check(st, q_dev, logp_dev);
+  if (!rc && (d < 1 || stage < 0 || stage > smc_max_stages(o))) rc = fail(EXMC_ERR_BADARG, "smc: bad arguments");
+  if (rc) return rc;
+  rc = select_device(device);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  return fail(EXMC_ERR_UNSUPPORTED, "smc: use libexmc_hip.so for the model-free front of a stage");
+#else
+  SmcScratch sc;
+  rc = sc.alloc(o.num_particles, n_runs, d);
+  if (!rc) rc = smc_stage_launch((hipStream_t)0, sc, o, n_runs, d, stage, q_dev, logp_dev, smc_runs(st));
+  if (rc) {
+    (void)hipStreamSynchronize((hipStream_t)0);   // the scratch is freed on return
+    return rc;
+  }
+  HIP_TRY(hipStreamSynchronize((hipStream_t)0));
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_smc(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* particles_dev,
+                 double* logp_dev, double* betas_dev, double* ess_history_dev, double* acceptance_rates_dev,
+                 int32_t* num_stages_dev, int32_t* status_dev) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  int rc = smc_opts_check(o, n_runs, run_lo);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)particles_dev; (void)logp_dev; (void)betas_dev; (void)ess_history_dev; (void)acceptance_rates_dev;
+  (void)num_stages_dev; (void)status_dev;
+  return fail(EXMC_ERR_UNSUPPORTED, "smc: a generated model goes through exmc_hip_smc_init, exmc_hip_smc_mutate and "
+              "libexmc_hip.so's exmc_hip_smc_reweight");
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const int lanes = resolve_lanes(m, o.lanes_per_chain);
+  const int N = o.num_particles, R = n_runs, d = m->d, max_stages = smc_max_stages(o);
+  const size_t C = (size_t)N * R, H = (size_t)max_stages * R;
+  // the state of the runs, and whatever the caller wants none of: scratch of the call
+  CallBuf own;
+  const size_t n_q = particles_dev ? 0 : (size_t)d * C, n_lp = logp_dev ? 0 : C;
+  const size_t n_b = betas_dev ? 0 : H, n_e = ess_history_dev ? 0 : H, n_a = acceptance_rates_dev ? 0 : H;
+  const size_t words8 = n_q + n_lp + n_b + n_e + n_a + 2 * C + (size_t)R + 2 * (size_t)R + (size_t)d * R;
+  rc = own.alloc(words8 * 8 + ((size_t)R + C + R + R + 1) * 4);
+  if (rc) return rc;
+  double* p = own.as<double>();
+  auto take8 = [&](size_t n) { double* r = p; p += n; return r; };
+  double* q = particles_dev ? particles_dev : take8(n_q);
+  double* lp = logp_dev ? logp_dev : take8(n_lp);
+  exmc_hip_smc_state st;
+  st.betas = betas_dev ? betas_dev : take8(n_b);
+  st.ess_history = ess_history_dev ? ess_history_dev : take8(n_e);
+  st.acceptance_rates = acceptance_rates_dev ? acceptance_rates_dev : take8(n_a);
+  uint64_t* words = (uint64_t*)take8(2 * C);
+  st.beta = take8(R);
+  st.run_rng = (uint64_t*)take8(2 * (size_t)R);
+  st.scale = take8((size_t)d * R);
+  int32_t* ip = (int32_t*)p;
+  st.active = ip;
+  st.accept = ip + R;
+  int32_t* own_ns = st.accept + C;
+  int32_t* own_status = own_ns + R;
+  st.active_count = own_status + R;
+  st.num_stages = num_stages_dev ? num_stages_dev : own_ns;
+  st.status = status_dev ? status_dev : own_status;
+  SmcScratch sc;
+  rc = sc.alloc(N, R, d);
+  if (rc) return rc;
+  const SmcParams P = smc_params(m, o, n_runs, run_lo, q, lp, words, st);
+  const SmcRuns runs = smc_runs(st);
+  float total_ms = 0.f;
+  auto run = [&]() -> int {
+    HIP_TRY(hipEventRecord(m->ev0, m->stream));
+    int rc2 = smc_model_launch<true>(m, lanes, P);
+    if (rc2) return rc2;
+    for (int stage = 0;; stage++) {   // the front at stage == max_stages only closes: its count is 0
+      rc2 = smc_stage_launch(m->stream, sc, o, n_runs, d, stage, q, lp, runs);
+      if (rc2) return rc2;
+      int32_t count = 0;
+      HIP_TRY(hipMemcpyAsync(&count, st.active_count, 4, hipMemcpyDeviceToHost, m->stream));
+      HIP_TRY(hipEventRecord(m->ev1, m->stream));
+      HIP_TRY(hipEventSynchronize(m->ev1));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+      total_ms += ms;
+      if (count == 0 || stage >= max_stages) return EXMC_OK;
+      HIP_TRY(hipEventRecord(m->ev0, m->stream));
+      rc2 = smc_model_launch<false>(m, lanes, P);
+      if (rc2) return rc2;
+    }
+  };
+  rc = run();
+  (void)hipStreamSynchronize(m->stream);   // before the scratch is freed
+  if (rc) return rc;
+  m->last_ms = total_ms;
+  return EXMC_OK;
+#endif
+}
+
+int exmc_hip_smc_host(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* particles,
+                      double* logp, double* betas, double* ess_history, double* acceptance_rates,
+                      int32_t* num_stages, int32_t* status) {
+  if (check_model(m)) return EXMC_ERR_BADARG;
+  int rc = smc_opts_check(o, n_runs, run_lo);
+  if (rc) return rc;
+#ifdef EXMC_ONLY_CUSTOM
+  (void)particles; (void)logp; (void)betas; (void)ess_history; (void)acceptance_rates; (void)num_stages; (void)status;
+  return fail(EXMC_ERR_UNSUPPORTED, "smc: a generated model goes through exmc_hip_smc_init, exmc_hip_smc_mutate and "
+              "libexmc_hip.so's exmc_hip_smc_reweight");
+#else
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t R = (size_t)n_runs, C = R * (size_t)o.num_particles, d = (size_t)m->d;
+  const size_t H = (size_t)smc_max_stages(o);
+  Scratch sc;
+  const auto s_q = sc.take<double>(particles ? d * C : 0);   // [d][C]
+  const auto s_lp = sc.take<double>(logp ? C : 0);
+  const auto s_b = sc.take<double>(betas ? H * R : 0), s_e = sc.take<double>(ess_history ? H * R : 0);
+  const auto s_a = sc.take<double>(acceptance_rates ? H * R : 0);
+  const auto s_ns = sc.take<int32_t>(R), s_st = sc.take<int32_t>(R);
+  rc = sc.alloc();
+  if (rc) return rc;
+  rc = exmc_hip_smc(m, o, n_runs, run_lo, particles ? sc.dev(s_q) : nullptr, logp ? sc.dev(s_lp) : nullptr,
+                    betas ? sc.dev(s_b) : nullptr, ess_history ? sc.dev(s_e) : nullptr,
+                    acceptance_rates ? sc.dev(s_a) : nullptr, sc.dev(s_ns), sc.dev(s_st));
+  if (!rc) rc = sc.download();
+  if (rc) return rc;
+  fits_first(sc.host(s_q), particles, d, C);   // [d][C] -> [R][N][d]
+  if (logp) std::copy(sc.host(s_lp), sc.host(s_lp) + C, logp);
+  fits_first(sc.host(s_b), betas, H, R);
+  fits_first(sc.host(s_e), ess_history, H, R);
+  fits_first(sc.host(s_a), acceptance_rates, H, R);
+  fits_first(sc.host(s_ns), num_stages, 1, R);
+  fits_first(sc.host(s_st), status, 1, R);
+  return EXMC_OK;
+#endif
+}
+
+}  // extern "C"
+
 // ---- importance diagnostics of the fits (include/exmc_hip_fit_psis.h; exmc_fit_psis.hpp, exmc_psis_ratio.hpp) ----
 namespace {
 
@@ -2944,7 +3244,7 @@ int ratio_launch(hipStream_t stream, const RatioScratch& sc, const double* lr, i
   if (n_resample < 1) return EXMC_OK;
   const long long lanes = (long long)Nb * sc.n_blocks;
   hipLaunchKernelGGL(ratio_scan_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, x, S, Nb, C,
-                     sc.n_blocks, sc.r.as<double>(), sc.tot.as<double>());
+                     sc.n_blocks, 0, sc.r.as<double>(), sc.tot.as<double>());
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(ratio_resample_kernel, dim3((unsigned)Nb), dim3(kRatioBlock), 0, stream, sc.r.as<double>(),
                      sc.tot.as<double>(), sc.base.as<double>(), S, Nb, C, sc.n_blocks, n_resample, seed,

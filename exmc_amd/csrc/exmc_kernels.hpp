@@ -241,6 +241,7 @@ __global__ void __launch_bounds__(kNutsBlock) find_eps_kernel(FindEpsParams P,
 #include "exmc_pathfinder.hpp"      // pathfinder_kernel: Exmc.Pathfinder, one L-BFGS path per lane group
 #include "exmc_advi.hpp"            // advi_kernel: Exmc.ADVI, one mean-field fit per lane group
 #include "exmc_fit_psis.hpp"        // fit_log_ratio_kernel: log p - log q of the fits' draws
+#include "exmc_smc.hpp"             // smc_init_kernel, smc_mutate_kernel: Exmc.SMC, one particle per lane group
 #ifndef EXMC_ONLY_CUSTOM            // a generated model's plug-in carries no predictive kernels
 #include "exmc_predictive.hpp"      // predictive_kernel: Exmc.Predictive, one chain's generator per lane
 #include "exmc_ppc.hpp"             // ppc_kernel: posterior predictive checks, the replicates reduced in place

@@ -13,7 +13,7 @@
   EXMC_PK_DECL __global__ void warmup_kernel<M, G, LDSL, PIPE>(WarmupParams, typename M::Consts);
 
 // part 5: the auxiliary kernels of a layout (vag_fn batches, chain init, the step-size search, Pathfinder, ADVI,
-// the fits' log ratios)
+// the fits' log ratios, the start and the mutation of SMC)
 #define EXMC_PK_AUX(M, G) \
   EXMC_PK_DECL __global__ void multi_step_kernel<M, G>(MultiStepParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void logp_grad_kernel<M, G>(const double*, int, double*, double*, typename M::Consts); \
@@ -21,7 +21,9 @@
   EXMC_PK_DECL __global__ void find_eps_kernel<M, G>(FindEpsParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void pathfinder_kernel<M, G>(PathfinderParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void advi_kernel<M, G>(AdviParams, typename M::Consts); \
-  EXMC_PK_DECL __global__ void fit_log_ratio_kernel<M, G>(FitLogRatioParams, typename M::Consts);
+  EXMC_PK_DECL __global__ void fit_log_ratio_kernel<M, G>(FitLogRatioParams, typename M::Consts); \
+  EXMC_PK_DECL __global__ void smc_init_kernel<M, G>(SmcParams, typename M::Consts); \
+  EXMC_PK_DECL __global__ void smc_mutate_kernel<M, G>(SmcParams, typename M::Consts);
 
 // and the chain init of a one-chain form (EXMC_ONE_CHAIN rows)
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 5

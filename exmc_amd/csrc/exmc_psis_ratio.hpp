@@ -15,7 +15,8 @@
 //                                  khat, (max lr + L1) - log n, exp(2 L1 - L2), n_zero, T; L1 (NaN for
 //                                  a NaN group) into l1[Nb]
 //   ratio_normalise_kernel         lw_k = x_k - L1 in place, NaN in a NaN group
-//   ratio_scan_kernel              w_k = exp(lw_k); one lane per block of kRatioScan consecutive samples
+//   ratio_scan_kernel              w_k = exp(lw_k) (or lw_k itself with `linear`: the caller's array holds
+//                                  the weights, exmc_smc.hpp); one lane per block of kRatioScan consecutive samples
 //                                  of a group: r_k = the running sum inside the block, left to right
 //                                  from 0.0, into r (the layout of lr); the block's total into tot[b][Nb]
 //   ratio_resample_kernel          one workgroup per group g: base_b = the earlier blocks' totals left to
@@ -24,6 +25,8 @@
 //                                  base_b + r_k >= pos_j (binary search over the blocks, then inside the
 //                                  block), n - 1 if there is none, -1 in a NaN group
 //   ratio_gather_kernel            out[j][r][g] = the draw idx[j][g] of the group, NaN where idx < 0
+// ratio_bases and ratio_search are the two steps of the resampling as device functions: the tempered
+// SMC (exmc_smc.hpp) searches the same cumulative sums with positions of its own.
 // Every output word has one writer; no atomics outside the tail kernel's LDS histogram.
 #pragma once
 
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(256) void ratio_normalise_kernel(double* __restrict
 
 // lane t: group t % Nb, block t / Nb
 __global__ __launch_bounds__(256) void ratio_scan_kernel(const double* __restrict__ lw, int S, int Nb, int C,
-                                                        int n_blocks, double* __restrict__ r_out,
+                                                        int n_blocks, int linear, double* __restrict__ r_out,
                                                         double* __restrict__ tot) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)Nb * n_blocks) return;
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(256) void ratio_scan_kernel(const double* __restric
   double r = 0.0;
   for (long long k = k0; k < k1; k++) {
     const size_t at = ((size_t)s * Nb + i) * C + c;
-    r = r + exmc_exp(lw[at]);
+    r = r + (linear ? lw[at] : exmc_exp(lw[at]));
     r_out[at] = r;
     if (++c == C) {
       c = 0;
@@ -150,6 +153,45 @@ __global__ __launch_bounds__(256) void ratio_scan_kernel(const double* __restric
     }
   }
   tot[(size_t)b * Nb + i] = r;
+}
+
+// bs[b] = the totals of the blocks before b of group i, left to right from 0.0; one lane writes them
+__device__ inline void ratio_bases(const double* __restrict__ tot, double* __restrict__ bs, int n_blocks, int Nb,
+                                   int i) {
+  double acc = 0.0;
+  bs[0] = acc;
+  for (int b = 0; b < n_blocks; b++) {
+    acc = acc + tot[(size_t)b * Nb + i];
+    bs[b + 1] = acc;
+  }
+}
+
+// the first sample k of group i with bs[block of k] + r_k >= pos (binary search over the blocks, then
+// inside the block), n - 1 if there is none
+__device__ inline long long ratio_search(const double* __restrict__ r, const double* __restrict__ bs, double pos,
+                                         long long n, int n_blocks, int Nb, int C, int i) {
+  int lo = 0, hi = n_blocks;   // the first block whose last cumulative value reaches pos
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (bs[mid + 1] >= pos) hi = mid;
+    else lo = mid + 1;
+  }
+  long long pick = n - 1;
+  if (lo < n_blocks) {
+    const double b0 = bs[lo];
+    long long ka = (long long)lo * kRatioScan;
+    long long kb = (ka + kRatioScan < n) ? ka + kRatioScan : n;
+    const long long kend = kb;
+    while (ka < kb) {
+      const long long mid = (ka + kb) >> 1;
+      const long long s = mid / C;
+      const int c = (int)(mid - s * C);
+      if (b0 + r[((size_t)s * Nb + i) * C + c] >= pos) kb = mid;
+      else ka = mid + 1;
+    }
+    pick = (ka < kend) ? ka : kend - 1;
+  }
+  return pick;
 }
 
 // base [Nb][n_blocks + 1] is scratch of the launch; idx [R][Nb]
@@ -166,42 +208,14 @@ __global__ __launch_bounds__(kRatioBlock) void ratio_resample_kernel(const doubl
     return;
   }
   double* bs = base + (size_t)i * ((size_t)n_blocks + 1);
-  if (tid == 0) {
-    double acc = 0.0;
-    bs[0] = acc;
-    for (int b = 0; b < n_blocks; b++) {
-      acc = acc + tot[(size_t)b * Nb + i];
-      bs[b + 1] = acc;
-    }
-  }
+  if (tid == 0) ratio_bases(tot, bs, n_blocks, Nb, i);
   __syncthreads();
   Rng rng;
   rng_seed(rng, seed + 7919ULL * (uint64_t)i);
   const double u = rng_uniform(rng);
   for (int j = tid; j < R; j += kRatioBlock) {
     const double pos = (u + (double)j) / (double)R;
-    int lo = 0, hi = n_blocks;   // the first block whose last cumulative value reaches pos
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (bs[mid + 1] >= pos) hi = mid;
-      else lo = mid + 1;
-    }
-    long long pick = n - 1;
-    if (lo < n_blocks) {
-      const double b0 = bs[lo];
-      long long ka = (long long)lo * kRatioScan;
-      long long kb = (ka + kRatioScan < n) ? ka + kRatioScan : n;
-      const long long kend = kb;
-      while (ka < kb) {
-        const long long mid = (ka + kb) >> 1;
-        const long long s = mid / C;
-        const int c = (int)(mid - s * C);
-        if (b0 + r[((size_t)s * Nb + i) * C + c] >= pos) kb = mid;
-        else ka = mid + 1;
-      }
-      pick = (ka < kend) ? ka : kend - 1;
-    }
-    idx[(size_t)j * Nb + i] = (int32_t)pick;
+    idx[(size_t)j * Nb + i] = (int32_t)ratio_search(r, bs, pos, n, n_blocks, Nb, C, i);
   }
 }
 
