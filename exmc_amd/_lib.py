@@ -52,6 +52,10 @@ ADVI_EXPORTS = ["exmc_hip_advi", "exmc_hip_advi_host"]
 SMC_EXPORTS = ["exmc_hip_smc_init", "exmc_hip_smc_mutate", "exmc_hip_smc_reweight", "exmc_hip_smc", "exmc_hip_smc_host"]
 SMC_DEFAULT_MAX_STAGES = 1000
 
+# include/exmc_hip_smc_bridge.h: bridged SMC, the start divided out of the weights, with a log evidence
+SMC_BRIDGE_EXPORTS = ["exmc_hip_smc_bridge_init", "exmc_hip_smc_bridge_mutate", "exmc_hip_smc_bridge_reweight",
+                      "exmc_hip_smc_bridge", "exmc_hip_smc_bridge_host"]
+
 # include/exmc_hip_fit_psis.h: the Pareto-smoothed importance ratios of the fits' draws and their resampling
 FIT_PSIS_EXPORTS = ["exmc_hip_fit_log_ratio", "exmc_hip_ratio_psis_from_lr", "exmc_hip_ratio_gather",
                     "exmc_hip_fit_psis", "exmc_hip_fit_psis_host"]
@@ -226,6 +230,11 @@ def bind(path):
     L.exmc_hip_smc_reweight.argtypes = [C.c_int, SmcOpts, C.c_int, C.c_int, C.c_int, vp, vp, SmcState]
     L.exmc_hip_smc.argtypes = [vp, SmcOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.exmc_hip_smc_host.argtypes = [vp, SmcOpts, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, ip]
+    L.exmc_hip_smc_bridge_init.argtypes = [vp, SmcOpts, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, SmcState, vp, vp]
+    L.exmc_hip_smc_bridge_mutate.argtypes = [vp, SmcOpts, C.c_int, vp, vp, vp, vp, vp, vp, SmcState]
+    L.exmc_hip_smc_bridge_reweight.argtypes = [C.c_int, SmcOpts, C.c_int, C.c_int, C.c_int, vp, vp, vp, SmcState, vp, vp]
+    L.exmc_hip_smc_bridge.argtypes = [vp, SmcOpts, C.c_int, C.c_int, vp, vp] + [vp] * 10
+    L.exmc_hip_smc_bridge_host.argtypes = [vp, SmcOpts, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip, dp, dp]
     L.exmc_hip_fit_log_ratio.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.exmc_hip_ratio_psis_from_lr.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp, vp]
     L.exmc_hip_ratio_gather.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]

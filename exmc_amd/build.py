@@ -48,6 +48,7 @@ DEPS = [
     os.path.join(ROOT, "include", "exmc_hip_pathfinder.h"),
     os.path.join(ROOT, "include", "exmc_hip_advi.h"),
     os.path.join(ROOT, "include", "exmc_hip_smc.h"),
+    os.path.join(ROOT, "include", "exmc_hip_smc_bridge.h"),
     os.path.join(ROOT, "include", "exmc_hip_fit_psis.h"),
     os.path.join(ROOT, "include", "exmc_hip_predictive.h"),
     os.path.join(ROOT, "include", "exmc_hip_ppc.h"),

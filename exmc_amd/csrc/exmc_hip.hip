@@ -12,6 +12,7 @@
 #include "../../include/exmc_hip_pathfinder.h"
 #include "../../include/exmc_hip_advi.h"
 #include "../../include/exmc_hip_smc.h"
+#include "../../include/exmc_hip_smc_bridge.h"
 #include "../../include/exmc_hip_fit_psis.h"
 #include "../../include/exmc_hip_predictive.h"
 #include "../../include/exmc_hip_ppc.h"
@@ -2850,7 +2851,7 @@ int exmc_hip_advi_host(exmc_hip_model* m, exmc_hip_advi_opts o, int n_fits, int 
 
 }  // extern "C"
 
-// ---- SMC (include/exmc_hip_smc.h; exmc_smc.hpp) --------------------------------------------------------
+// ---- SMC and its bridged mode (include/exmc_hip_smc.h, exmc_hip_smc_bridge.h; exmc_smc.hpp) ------------------
 namespace {
 
 int smc_max_stages(const exmc_hip_smc_opts& o) { return o.max_stages > 0 ? o.max_stages : EXMC_SMC_DEFAULT_MAX_STAGES; }
@@ -2894,13 +2895,22 @@ SmcParams smc_params(exmc_hip_model* m, const exmc_hip_smc_opts& o, int n_runs, 
   return P;
 }
 
-// smc_init_kernel or smc_mutate_kernel of the handle's layout on its stream; the caller records the events
+// smc_init_kernel or smc_mutate_kernel of the handle's layout on its stream, with `B` their bridged siblings;
+// the caller records the events
 template <bool kInit>
-int smc_model_launch(exmc_hip_model* m, int lanes, const SmcParams& P) {
+int smc_model_launch(exmc_hip_model* m, int lanes, const SmcParams& P, const SmcBridge* B = nullptr) {
   return dispatch(m, lanes, [&](auto tag, const auto& mc) {
     using T = decltype(tag);
     const size_t xlds = aux_lds_bytes<typename T::M>();
-    if constexpr (kInit) {
+    if (B) {
+      if constexpr (kInit) {
+        EXMC_KLAUNCH(m->device, (smc_bridge_init_kernel<typename T::M, T::G>), grid_for(P.n_chains, T::G, kBlock),
+                     dim3(kBlock), xlds, m->stream, P, *B, mc);
+      } else {
+        EXMC_KLAUNCH(m->device, (smc_bridge_mutate_kernel<typename T::M, T::G>), grid_for(P.n_chains, T::G, kBlock),
+                     dim3(kBlock), xlds, m->stream, P, *B, mc);
+      }
+    } else if constexpr (kInit) {
       EXMC_KLAUNCH(m->device, (smc_init_kernel<typename T::M, T::G>), grid_for(P.n_chains, T::G, kBlock), dim3(kBlock),
                    xlds, m->stream, P, mc);
     } else {
@@ -2917,13 +2927,13 @@ int smc_model_launch(exmc_hip_model* m, int lanes, const SmcParams& P) {
 struct SmcScratch {
   CallBuf buf;
   int n_blocks = 0;
-  double *nw = nullptr, *rcum = nullptr, *tot = nullptr, *base = nullptr, *q2 = nullptr, *lp2 = nullptr;
+  double *nw = nullptr, *rcum = nullptr, *tot = nullptr, *base = nullptr, *q2 = nullptr, *lp2 = nullptr, *lb2 = nullptr;
   int32_t *resample = nullptr, *idx = nullptr;
-  int alloc(int N, int R, int d) {
+  int alloc(int N, int R, int d, bool bridge = false) {
     const size_t C = (size_t)N * R;
     n_blocks = (N + kRatioScan - 1) / kRatioScan;
     const size_t n_tot = (size_t)n_blocks * R, n_base = ((size_t)n_blocks + 1) * R;
-    const size_t doubles = C + C + n_tot + n_base + (size_t)d * C + C;
+    const size_t doubles = C + C + n_tot + n_base + (size_t)d * C + C + (bridge ? C : 0);
     int rc = buf.alloc(doubles * 8 + ((size_t)R + C) * 4);
     if (rc) return rc;
     nw = buf.as<double>();
@@ -2932,22 +2942,29 @@ struct SmcScratch {
     base = tot + n_tot;
     q2 = base + n_base;
     lp2 = q2 + (size_t)d * C;
-    resample = (int32_t*)(lp2 + C);
+    lb2 = lp2 + C;
+    resample = (int32_t*)(lb2 + (bridge ? C : 0));
     idx = resample + R;
     return EXMC_OK;
   }
 };
 
-// exmc_hip_smc_reweight's launches for one stage
+// exmc_hip_smc_reweight's launches for one stage; with `B` exmc_hip_smc_bridge_reweight's
 int smc_stage_launch(hipStream_t stream, const SmcScratch& sc, const exmc_hip_smc_opts& o, int n_runs, int d, int stage,
-                     double* q, double* logp, const SmcRuns& runs) {
+                     double* q, double* logp, const SmcRuns& runs, const SmcBridge* B = nullptr) {
   const int N = o.num_particles, R = n_runs, max_stages = smc_max_stages(o);
   const long long C = (long long)N * R;
   const SmcStage S{N, R, stage, max_stages, o.num_mh_steps, o.threshold_ratio * (double)N, d, std::sqrt((double)d), runs};
   hipLaunchKernelGGL(smc_close_kernel, dim3(1), dim3(kSmcBlock), 0, stream, S);
   HIP_TRY(hipGetLastError());
   if (stage >= max_stages) return EXMC_OK;
-  if (N <= kSmcLdsParticles)
+  if (B && N <= kSmcLdsParticles)
+    hipLaunchKernelGGL(smc_bridge_weights_kernel<true>, dim3((unsigned)R), dim3(kSmcBlock), (size_t)N * 8, stream, S, logp,
+                       *B, sc.nw, sc.resample);
+  else if (B)
+    hipLaunchKernelGGL(smc_bridge_weights_kernel<false>, dim3((unsigned)R), dim3(kSmcBlock), 0, stream, S, logp, *B, sc.nw,
+                       sc.resample);
+  else if (N <= kSmcLdsParticles)
     hipLaunchKernelGGL(smc_weights_kernel<true>, dim3((unsigned)R), dim3(kSmcBlock), (size_t)N * 8, stream, S, logp, sc.nw,
                        sc.resample);
   else
@@ -2961,58 +2978,73 @@ int smc_stage_launch(hipStream_t stream, const SmcScratch& sc, const exmc_hip_sm
   hipLaunchKernelGGL(smc_resample_kernel, dim3((unsigned)R), dim3(kSmcBlock), 0, stream, S, sc.rcum, sc.tot, sc.base,
                      sc.n_blocks, sc.resample, sc.idx);
   HIP_TRY(hipGetLastError());
-  const long long total = ((long long)d + 1) * C;
-  hipLaunchKernelGGL(smc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, q, logp, sc.idx, d,
-                     N, C, sc.q2, sc.lp2);
+  const long long total = ((long long)d + (B ? 2 : 1)) * C;
+  hipLaunchKernelGGL(smc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, q, logp,
+                     B ? B->logb : nullptr, sc.idx, d, N, C, sc.q2, sc.lp2, B ? sc.lb2 : nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(q, sc.q2, (size_t)d * C * 8, hipMemcpyDeviceToDevice, stream));
   HIP_TRY(hipMemcpyAsync(logp, sc.lp2, (size_t)C * 8, hipMemcpyDeviceToDevice, stream));
+  if (B) HIP_TRY(hipMemcpyAsync(B->logb, sc.lb2, (size_t)C * 8, hipMemcpyDeviceToDevice, stream));
   hipLaunchKernelGGL(smc_scale_kernel, dim3((unsigned)R, (unsigned)d), dim3(kSmcBlock), 0, stream, S, q, C);
   HIP_TRY(hipGetLastError());
   return EXMC_OK;
 }
 #endif
 
-}  // namespace
 
-extern "C" {
+// ---- the bridged mode's arguments (include/exmc_hip_smc_bridge.h) ----
+// the base read back and checked: finite mu, finite sigma > 0
+int smc_base_check(const double* mu_dev, const double* sigma_dev, int d) {
+  std::vector<double> h((size_t)d);
+  for (const double* a : {mu_dev, sigma_dev}) {
+    if (!a) continue;
+    HIP_TRY(hipMemcpy(h.data(), a, (size_t)d * 8, hipMemcpyDeviceToHost));
+    for (double v : h)
+      if (!std::isfinite(v) || (a == sigma_dev && !(v > 0.0)))
+        return fail(EXMC_ERR_BADARG, "smc bridge: the base needs finite mu and finite sigma > 0");
+  }
+  return EXMC_OK;
+}
 
-int exmc_hip_smc_init(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* q_dev,
-                      double* logp_dev, uint64_t* rng_words_dev, exmc_hip_smc_state st) {
+SmcBridge smc_bridge(int d, const double* mu, const double* sigma, double* logb, double* log_evidence, double* steps) {
+  return SmcBridge{mu, sigma, 0.5 * d * std::log(2.0 * M_PI), logb, log_evidence, steps};
+}
+
+int smc_bridge_check(const double* logb, const double* log_evidence, const double* steps) {
+  if (!logb || !log_evidence || !steps)
+    return fail(EXMC_ERR_BADARG, "smc bridge: logb, log_evidence and log_evidence_steps are required");
+  return EXMC_OK;
+}
+
+// exmc_hip_smc_init / _mutate and their bridged forms (B)
+template <bool kInit>
+int smc_model_step(exmc_hip_model* m, const exmc_hip_smc_opts& o, int n_runs, int run_lo, double* q_dev, double* logp_dev,
+                   uint64_t* rng_words_dev, const exmc_hip_smc_state& st, const SmcBridge* B) {
   if (check_model(m)) return EXMC_ERR_BADARG;
   int rc = smc_opts_check(o, n_runs, run_lo);
   if (!rc) rc = smc_state_check(st, q_dev, logp_dev);
   if (!rc && !rng_words_dev) rc = fail(EXMC_ERR_BADARG, "smc: the arrays of the state are all required");
+  if (!rc && B && kInit) rc = smc_bridge_check(B->logb, B->log_evidence, B->log_evidence_steps);
+  if (!rc && B && !B->logb) rc = fail(EXMC_ERR_BADARG, "smc bridge: logb is required");   // the mutation writes no evidence
   if (rc) return rc;
   HIP_TRY(hipSetDevice(m->device));
+  if (B && kInit) {
+    rc = smc_base_check(B->mu, B->sigma, m->d);
+    if (rc) return rc;
+  }
   const SmcParams P = smc_params(m, o, n_runs, run_lo, q_dev, logp_dev, rng_words_dev, st);
   HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  rc = smc_model_launch<true>(m, resolve_lanes(m, o.lanes_per_chain), P);
+  rc = smc_model_launch<kInit>(m, resolve_lanes(m, o.lanes_per_chain), P, B);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(m->ev1, m->stream));
   return finish_timing(m);   // waits for the launch
 }
 
-int exmc_hip_smc_mutate(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, double* q_dev, double* logp_dev,
-                        uint64_t* rng_words_dev, exmc_hip_smc_state st) {
-  if (check_model(m)) return EXMC_ERR_BADARG;
+int smc_reweight(int device, const exmc_hip_smc_opts& o, int n_runs, int d, int stage, double* q_dev, double* logp_dev,
+                 const exmc_hip_smc_state& st, const SmcBridge* B) {
   int rc = smc_opts_check(o, n_runs, 0);
   if (!rc) rc = smc_state_check(st, q_dev, logp_dev);
-  if (!rc && !rng_words_dev) rc = fail(EXMC_ERR_BADARG, "smc: the arrays of the state are all required");
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  const SmcParams P = smc_params(m, o, n_runs, 0, q_dev, logp_dev, rng_words_dev, st);
-  HIP_TRY(hipEventRecord(m->ev0, m->stream));
-  rc = smc_model_launch<false>(m, resolve_lanes(m, o.lanes_per_chain), P);
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(m->ev1, m->stream));
-  return finish_timing(m);   // waits for the launch
-}
-
-int exmc_hip_smc_reweight(int device, exmc_hip_smc_opts o, int n_runs, int d, int stage, double* q_dev,
-                          double* logp_dev, exmc_hip_smc_state st) {
-  int rc = smc_opts_check(o, n_runs, 0);
-  if (!rc) rc = smc_state_check(st, q_dev, logp_dev);
+  if (!rc && B) rc = smc_bridge_check(B->logb, B->log_evidence, B->log_evidence_steps);
   if (!rc && (d < 1 || stage < 0 || stage > smc_max_stages(o))) rc = fail(EXMC_ERR_BADARG, "smc: bad arguments");
   if (rc) return rc;
   rc = select_device(device);
@@ -3021,8 +3053,8 @@ int exmc_hip_smc_reweight(int device, exmc_hip_smc_opts o, int n_runs, int d, in
   return fail(EXMC_ERR_UNSUPPORTED, "smc: use libexmc_hip.so for the model-free front of a stage");
 #else
   SmcScratch sc;
-  rc = sc.alloc(o.num_particles, n_runs, d);
-  if (!rc) rc = smc_stage_launch((hipStream_t)0, sc, o, n_runs, d, stage, q_dev, logp_dev, smc_runs(st));
+  rc = sc.alloc(o.num_particles, n_runs, d, B != nullptr);
+  if (!rc) rc = smc_stage_launch((hipStream_t)0, sc, o, n_runs, d, stage, q_dev, logp_dev, smc_runs(st), B);
   if (rc) {
     (void)hipStreamSynchronize((hipStream_t)0);   // the scratch is freed on return
     return rc;
@@ -3032,37 +3064,61 @@ int exmc_hip_smc_reweight(int device, exmc_hip_smc_opts o, int n_runs, int d, in
 #endif
 }
 
-int exmc_hip_smc(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* particles_dev,
-                 double* logp_dev, double* betas_dev, double* ess_history_dev, double* acceptance_rates_dev,
-                 int32_t* num_stages_dev, int32_t* status_dev) {
+// the outputs of a whole run, device or host; the last three are the bridged mode's
+struct SmcOuts {
+  double *particles, *logp, *betas, *ess_history, *acceptance_rates;
+  int32_t *num_stages, *status;
+  double *logb, *log_evidence, *log_evidence_steps;
+};
+
+#ifdef EXMC_ONLY_CUSTOM
+const char* const kSmcPluginWhole = "smc: a generated model goes through exmc_hip_smc_init, exmc_hip_smc_mutate and "
+                                    "libexmc_hip.so's exmc_hip_smc_reweight, or their bridged forms";
+#endif
+
+// exmc_hip_smc, and exmc_hip_smc_bridge with `base` (its mu, sigma and log_norm; the arrays come from `out`)
+int smc_whole(exmc_hip_model* m, const exmc_hip_smc_opts& o, int n_runs, int run_lo, const SmcOuts& out,
+              const SmcBridge* base) {
   if (check_model(m)) return EXMC_ERR_BADARG;
   int rc = smc_opts_check(o, n_runs, run_lo);
   if (rc) return rc;
 #ifdef EXMC_ONLY_CUSTOM
-  (void)particles_dev; (void)logp_dev; (void)betas_dev; (void)ess_history_dev; (void)acceptance_rates_dev;
-  (void)num_stages_dev; (void)status_dev;
-  return fail(EXMC_ERR_UNSUPPORTED, "smc: a generated model goes through exmc_hip_smc_init, exmc_hip_smc_mutate and "
-              "libexmc_hip.so's exmc_hip_smc_reweight");
+  (void)out; (void)base;
+  return fail(EXMC_ERR_UNSUPPORTED, kSmcPluginWhole);
 #else
   HIP_TRY(hipSetDevice(m->device));
+  if (base) {
+    rc = smc_base_check(base->mu, base->sigma, m->d);
+    if (rc) return rc;
+  }
   const int lanes = resolve_lanes(m, o.lanes_per_chain);
   const int N = o.num_particles, R = n_runs, d = m->d, max_stages = smc_max_stages(o);
   const size_t C = (size_t)N * R, H = (size_t)max_stages * R;
   // the state of the runs, and whatever the caller wants none of: scratch of the call
   CallBuf own;
-  const size_t n_q = particles_dev ? 0 : (size_t)d * C, n_lp = logp_dev ? 0 : C;
-  const size_t n_b = betas_dev ? 0 : H, n_e = ess_history_dev ? 0 : H, n_a = acceptance_rates_dev ? 0 : H;
-  const size_t words8 = n_q + n_lp + n_b + n_e + n_a + 2 * C + (size_t)R + 2 * (size_t)R + (size_t)d * R;
+  const size_t n_q = out.particles ? 0 : (size_t)d * C, n_lp = out.logp ? 0 : C;
+  const size_t n_b = out.betas ? 0 : H, n_e = out.ess_history ? 0 : H, n_a = out.acceptance_rates ? 0 : H;
+  const size_t n_lb = (base && !out.logb) ? C : 0, n_le = (base && !out.log_evidence) ? (size_t)R : 0;
+  const size_t n_les = (base && !out.log_evidence_steps) ? H : 0;
+  const size_t words8 = n_q + n_lp + n_b + n_e + n_a + n_lb + n_le + n_les + 2 * C + (size_t)R + 2 * (size_t)R + (size_t)d * R;
   rc = own.alloc(words8 * 8 + ((size_t)R + C + R + R + 1) * 4);
   if (rc) return rc;
   double* p = own.as<double>();
   auto take8 = [&](size_t n) { double* r = p; p += n; return r; };
-  double* q = particles_dev ? particles_dev : take8(n_q);
-  double* lp = logp_dev ? logp_dev : take8(n_lp);
+  double* q = out.particles ? out.particles : take8(n_q);
+  double* lp = out.logp ? out.logp : take8(n_lp);
   exmc_hip_smc_state st;
-  st.betas = betas_dev ? betas_dev : take8(n_b);
-  st.ess_history = ess_history_dev ? ess_history_dev : take8(n_e);
-  st.acceptance_rates = acceptance_rates_dev ? acceptance_rates_dev : take8(n_a);
+  st.betas = out.betas ? out.betas : take8(n_b);
+  st.ess_history = out.ess_history ? out.ess_history : take8(n_e);
+  st.acceptance_rates = out.acceptance_rates ? out.acceptance_rates : take8(n_a);
+  SmcBridge bridge{};
+  if (base) {
+    bridge = *base;
+    bridge.logb = out.logb ? out.logb : take8(n_lb);
+    bridge.log_evidence = out.log_evidence ? out.log_evidence : take8(n_le);
+    bridge.log_evidence_steps = out.log_evidence_steps ? out.log_evidence_steps : take8(n_les);
+  }
+  const SmcBridge* B = base ? &bridge : nullptr;
   uint64_t* words = (uint64_t*)take8(2 * C);
   st.beta = take8(R);
   st.run_rng = (uint64_t*)take8(2 * (size_t)R);
@@ -3073,20 +3129,20 @@ int exmc_hip_smc(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo,
   int32_t* own_ns = st.accept + C;
   int32_t* own_status = own_ns + R;
   st.active_count = own_status + R;
-  st.num_stages = num_stages_dev ? num_stages_dev : own_ns;
-  st.status = status_dev ? status_dev : own_status;
+  st.num_stages = out.num_stages ? out.num_stages : own_ns;
+  st.status = out.status ? out.status : own_status;
   SmcScratch sc;
-  rc = sc.alloc(N, R, d);
+  rc = sc.alloc(N, R, d, base != nullptr);
   if (rc) return rc;
   const SmcParams P = smc_params(m, o, n_runs, run_lo, q, lp, words, st);
   const SmcRuns runs = smc_runs(st);
   float total_ms = 0.f;
   auto run = [&]() -> int {
     HIP_TRY(hipEventRecord(m->ev0, m->stream));
-    int rc2 = smc_model_launch<true>(m, lanes, P);
+    int rc2 = smc_model_launch<true>(m, lanes, P, B);
     if (rc2) return rc2;
     for (int stage = 0;; stage++) {   // the front at stage == max_stages only closes: its count is 0
-      rc2 = smc_stage_launch(m->stream, sc, o, n_runs, d, stage, q, lp, runs);
+      rc2 = smc_stage_launch(m->stream, sc, o, n_runs, d, stage, q, lp, runs, B);
       if (rc2) return rc2;
       int32_t count = 0;
       HIP_TRY(hipMemcpyAsync(&count, st.active_count, 4, hipMemcpyDeviceToHost, m->stream));
@@ -3097,7 +3153,7 @@ int exmc_hip_smc(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo,
       total_ms += ms;
       if (count == 0 || stage >= max_stages) return EXMC_OK;
       HIP_TRY(hipEventRecord(m->ev0, m->stream));
-      rc2 = smc_model_launch<false>(m, lanes, P);
+      rc2 = smc_model_launch<false>(m, lanes, P, B);
       if (rc2) return rc2;
     }
   };
@@ -3109,42 +3165,144 @@ int exmc_hip_smc(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo,
 #endif
 }
 
-int exmc_hip_smc_host(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* particles,
-                      double* logp, double* betas, double* ess_history, double* acceptance_rates,
-                      int32_t* num_stages, int32_t* status) {
+// exmc_hip_smc_host, and exmc_hip_smc_bridge_host with `bridge`: mu and sigma are host arrays [d] or null
+int smc_whole_host(exmc_hip_model* m, const exmc_hip_smc_opts& o, int n_runs, int run_lo, const SmcOuts& out,
+                   bool bridge, const double* mu, const double* sigma) {
   if (check_model(m)) return EXMC_ERR_BADARG;
   int rc = smc_opts_check(o, n_runs, run_lo);
   if (rc) return rc;
 #ifdef EXMC_ONLY_CUSTOM
-  (void)particles; (void)logp; (void)betas; (void)ess_history; (void)acceptance_rates; (void)num_stages; (void)status;
-  return fail(EXMC_ERR_UNSUPPORTED, "smc: a generated model goes through exmc_hip_smc_init, exmc_hip_smc_mutate and "
-              "libexmc_hip.so's exmc_hip_smc_reweight");
+  (void)out; (void)bridge; (void)mu; (void)sigma;
+  return fail(EXMC_ERR_UNSUPPORTED, kSmcPluginWhole);
 #else
   HIP_TRY(hipSetDevice(m->device));
   const size_t R = (size_t)n_runs, C = R * (size_t)o.num_particles, d = (size_t)m->d;
   const size_t H = (size_t)smc_max_stages(o);
   Scratch sc;
-  const auto s_q = sc.take<double>(particles ? d * C : 0);   // [d][C]
-  const auto s_lp = sc.take<double>(logp ? C : 0);
-  const auto s_b = sc.take<double>(betas ? H * R : 0), s_e = sc.take<double>(ess_history ? H * R : 0);
-  const auto s_a = sc.take<double>(acceptance_rates ? H * R : 0);
+  const auto s_q = sc.take<double>(out.particles ? d * C : 0);   // [d][C]
+  const auto s_lp = sc.take<double>(out.logp ? C : 0);
+  const auto s_b = sc.take<double>(out.betas ? H * R : 0), s_e = sc.take<double>(out.ess_history ? H * R : 0);
+  const auto s_a = sc.take<double>(out.acceptance_rates ? H * R : 0);
+  const auto s_lb = sc.take<double>(out.logb ? C : 0), s_le = sc.take<double>(out.log_evidence ? R : 0);
+  const auto s_les = sc.take<double>(out.log_evidence_steps ? H * R : 0);
   const auto s_ns = sc.take<int32_t>(R), s_st = sc.take<int32_t>(R);
   rc = sc.alloc();
   if (rc) return rc;
-  rc = exmc_hip_smc(m, o, n_runs, run_lo, particles ? sc.dev(s_q) : nullptr, logp ? sc.dev(s_lp) : nullptr,
-                    betas ? sc.dev(s_b) : nullptr, ess_history ? sc.dev(s_e) : nullptr,
-                    acceptance_rates ? sc.dev(s_a) : nullptr, sc.dev(s_ns), sc.dev(s_st));
+  CallBuf base_buf;
+  SmcBridge base = smc_bridge(m->d, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (bridge && (mu || sigma)) {
+    rc = base_buf.alloc(2 * d * 8);
+    if (rc) return rc;
+    if (mu) {
+      HIP_TRY(hipMemcpy(base_buf.as<double>(), mu, d * 8, hipMemcpyHostToDevice));
+      base.mu = base_buf.as<double>();
+    }
+    if (sigma) {
+      HIP_TRY(hipMemcpy(base_buf.as<double>() + d, sigma, d * 8, hipMemcpyHostToDevice));
+      base.sigma = base_buf.as<double>() + d;
+    }
+  }
+  const SmcOuts dev{out.particles ? sc.dev(s_q) : nullptr, out.logp ? sc.dev(s_lp) : nullptr,
+                    out.betas ? sc.dev(s_b) : nullptr, out.ess_history ? sc.dev(s_e) : nullptr,
+                    out.acceptance_rates ? sc.dev(s_a) : nullptr, sc.dev(s_ns), sc.dev(s_st),
+                    out.logb ? sc.dev(s_lb) : nullptr, out.log_evidence ? sc.dev(s_le) : nullptr,
+                    out.log_evidence_steps ? sc.dev(s_les) : nullptr};
+  rc = smc_whole(m, o, n_runs, run_lo, dev, bridge ? &base : nullptr);
   if (!rc) rc = sc.download();
   if (rc) return rc;
-  fits_first(sc.host(s_q), particles, d, C);   // [d][C] -> [R][N][d]
-  if (logp) std::copy(sc.host(s_lp), sc.host(s_lp) + C, logp);
-  fits_first(sc.host(s_b), betas, H, R);
-  fits_first(sc.host(s_e), ess_history, H, R);
-  fits_first(sc.host(s_a), acceptance_rates, H, R);
-  fits_first(sc.host(s_ns), num_stages, 1, R);
-  fits_first(sc.host(s_st), status, 1, R);
+  fits_first(sc.host(s_q), out.particles, d, C);   // [d][C] -> [R][N][d]
+  if (out.logp) std::copy(sc.host(s_lp), sc.host(s_lp) + C, out.logp);
+  fits_first(sc.host(s_b), out.betas, H, R);
+  fits_first(sc.host(s_e), out.ess_history, H, R);
+  fits_first(sc.host(s_a), out.acceptance_rates, H, R);
+  fits_first(sc.host(s_ns), out.num_stages, 1, R);
+  fits_first(sc.host(s_st), out.status, 1, R);
+  if (out.logb) std::copy(sc.host(s_lb), sc.host(s_lb) + C, out.logb);
+  if (out.log_evidence) std::copy(sc.host(s_le), sc.host(s_le) + R, out.log_evidence);
+  fits_first(sc.host(s_les), out.log_evidence_steps, H, R);
   return EXMC_OK;
 #endif
+}
+
+}  // namespace
+
+extern "C" {
+
+int exmc_hip_smc_init(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* q_dev,
+                      double* logp_dev, uint64_t* rng_words_dev, exmc_hip_smc_state st) {
+  return smc_model_step<true>(m, o, n_runs, run_lo, q_dev, logp_dev, rng_words_dev, st, nullptr);
+}
+
+int exmc_hip_smc_mutate(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, double* q_dev, double* logp_dev,
+                        uint64_t* rng_words_dev, exmc_hip_smc_state st) {
+  return smc_model_step<false>(m, o, n_runs, 0, q_dev, logp_dev, rng_words_dev, st, nullptr);
+}
+
+int exmc_hip_smc_reweight(int device, exmc_hip_smc_opts o, int n_runs, int d, int stage, double* q_dev,
+                          double* logp_dev, exmc_hip_smc_state st) {
+  return smc_reweight(device, o, n_runs, d, stage, q_dev, logp_dev, st, nullptr);
+}
+
+int exmc_hip_smc(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* particles_dev,
+                 double* logp_dev, double* betas_dev, double* ess_history_dev, double* acceptance_rates_dev,
+                 int32_t* num_stages_dev, int32_t* status_dev) {
+  return smc_whole(m, o, n_runs, run_lo,
+                   SmcOuts{particles_dev, logp_dev, betas_dev, ess_history_dev, acceptance_rates_dev, num_stages_dev,
+                           status_dev, nullptr, nullptr, nullptr},
+                   nullptr);
+}
+
+int exmc_hip_smc_host(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, double* particles,
+                      double* logp, double* betas, double* ess_history, double* acceptance_rates,
+                      int32_t* num_stages, int32_t* status) {
+  return smc_whole_host(m, o, n_runs, run_lo,
+                        SmcOuts{particles, logp, betas, ess_history, acceptance_rates, num_stages, status, nullptr,
+                                nullptr, nullptr},
+                        false, nullptr, nullptr);
+}
+
+int exmc_hip_smc_bridge_init(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, const double* mu_dev,
+                             const double* sigma_dev, double* q_dev, double* logp_dev, double* logb_dev,
+                             uint64_t* rng_words_dev, exmc_hip_smc_state st, double* log_evidence_dev,
+                             double* log_evidence_steps_dev) {
+  const SmcBridge B = smc_bridge(m ? m->d : 0, mu_dev, sigma_dev, logb_dev, log_evidence_dev, log_evidence_steps_dev);
+  return smc_model_step<true>(m, o, n_runs, run_lo, q_dev, logp_dev, rng_words_dev, st, &B);
+}
+
+int exmc_hip_smc_bridge_mutate(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, const double* mu_dev,
+                               const double* sigma_dev, double* q_dev, double* logp_dev, double* logb_dev,
+                               uint64_t* rng_words_dev, exmc_hip_smc_state st) {
+  const SmcBridge B = smc_bridge(m ? m->d : 0, mu_dev, sigma_dev, logb_dev, nullptr, nullptr);
+  return smc_model_step<false>(m, o, n_runs, 0, q_dev, logp_dev, rng_words_dev, st, &B);
+}
+
+int exmc_hip_smc_bridge_reweight(int device, exmc_hip_smc_opts o, int n_runs, int d, int stage, double* q_dev,
+                                 double* logp_dev, double* logb_dev, exmc_hip_smc_state st, double* log_evidence_dev,
+                                 double* log_evidence_steps_dev) {
+  const SmcBridge B = smc_bridge(d, nullptr, nullptr, logb_dev, log_evidence_dev, log_evidence_steps_dev);
+  return smc_reweight(device, o, n_runs, d, stage, q_dev, logp_dev, st, &B);
+}
+
+int exmc_hip_smc_bridge(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, const double* mu_dev,
+                        const double* sigma_dev, double* particles_dev, double* logp_dev, double* logb_dev,
+                        double* betas_dev, double* ess_history_dev, double* acceptance_rates_dev,
+                        int32_t* num_stages_dev, int32_t* status_dev, double* log_evidence_dev,
+                        double* log_evidence_steps_dev) {
+  const SmcBridge base = smc_bridge(m ? m->d : 0, mu_dev, sigma_dev, nullptr, nullptr, nullptr);
+  return smc_whole(m, o, n_runs, run_lo,
+                   SmcOuts{particles_dev, logp_dev, betas_dev, ess_history_dev, acceptance_rates_dev, num_stages_dev,
+                           status_dev, logb_dev, log_evidence_dev, log_evidence_steps_dev},
+                   &base);
+}
+
+int exmc_hip_smc_bridge_host(exmc_hip_model* m, exmc_hip_smc_opts o, int n_runs, int run_lo, const double* mu,
+                             const double* sigma, double* particles, double* logp, double* logb, double* betas,
+                             double* ess_history, double* acceptance_rates, int32_t* num_stages, int32_t* status,
+                             double* log_evidence, double* log_evidence_steps) {
+  return smc_whole_host(m, o, n_runs, run_lo,
+                        SmcOuts{particles, logp, betas, ess_history, acceptance_rates, num_stages, status, logb,
+                                log_evidence, log_evidence_steps},
+                        true, mu, sigma);
 }
 
 }  // extern "C"

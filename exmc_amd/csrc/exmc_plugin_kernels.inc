@@ -13,7 +13,7 @@
   EXMC_PK_DECL __global__ void warmup_kernel<M, G, LDSL, PIPE>(WarmupParams, typename M::Consts);
 
 // part 5: the auxiliary kernels of a layout (vag_fn batches, chain init, the step-size search, Pathfinder, ADVI,
-// the fits' log ratios, the start and the mutation of SMC)
+// the fits' log ratios, the start and the mutation of SMC and of its bridged mode)
 #define EXMC_PK_AUX(M, G) \
   EXMC_PK_DECL __global__ void multi_step_kernel<M, G>(MultiStepParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void logp_grad_kernel<M, G>(const double*, int, double*, double*, typename M::Consts); \
@@ -23,7 +23,9 @@
   EXMC_PK_DECL __global__ void advi_kernel<M, G>(AdviParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void fit_log_ratio_kernel<M, G>(FitLogRatioParams, typename M::Consts); \
   EXMC_PK_DECL __global__ void smc_init_kernel<M, G>(SmcParams, typename M::Consts); \
-  EXMC_PK_DECL __global__ void smc_mutate_kernel<M, G>(SmcParams, typename M::Consts);
+  EXMC_PK_DECL __global__ void smc_mutate_kernel<M, G>(SmcParams, typename M::Consts); \
+  EXMC_PK_DECL __global__ void smc_bridge_init_kernel<M, G>(SmcParams, SmcBridge, typename M::Consts); \
+  EXMC_PK_DECL __global__ void smc_bridge_mutate_kernel<M, G>(SmcParams, SmcBridge, typename M::Consts);
 
 // and the chain init of a one-chain form (EXMC_ONE_CHAIN rows)
 #if !defined(EXMC_PLUGIN_PART) || EXMC_PLUGIN_PART == 5

@@ -37,6 +37,11 @@
 // lane groups past C shadow the last one in the co-operative kinds and store nothing. The model-free
 // kernels (not in a plug-in): one workgroup of kSmcBlock lanes per run, or per (run, dimension).
 // Vector stores only, one writer per output word, no floating-point atomics.
+//
+// The bridged mode (DESIGN.md "Bridged SMC", include/exmc_hip_smc_bridge.h, tests/smc_bridge_statement.py)
+// tempers along log pi_beta = beta logp + (1 - beta) log q0 from a diagonal-normal base q0 and estimates the
+// log evidence. Its kernels are siblings of the ones above over the same bodies (smc_init_body,
+// smc_mutate_body, smc_weights_body with kBridge); what they add travels in SmcBridge.
 #pragma once
 
 #include "exmc_kernels.hpp"   // attach_scratch, the launch shape of init_chains_kernel
@@ -79,13 +84,41 @@ struct SmcParams {
   FlatOrder flat;
 };
 
+// What the bridged mode adds to a call (DESIGN.md "Bridged SMC", include/exmc_hip_smc_bridge.h): the base
+// q0 = N(mu, diag sigma^2) in kernel order, shared by the runs of the call, lb = log q0 of every particle and
+// the evidence. The temper runs along log pi_beta = beta logp + (1 - beta) log q0.
+struct SmcBridge {
+  const double* mu;             // [D] or null: 0.0
+  const double* sigma;          // [D] or null: 0.5
+  double log_norm;              // 0.5 * d * log(2.0 * pi), libm on the host
+  double* logb;                 // [C]
+  double* log_evidence;         // [R]
+  double* log_evidence_steps;   // [max_stages][R]
+};
+
+// log q0 in the EXMC_FIT_SIGMA form of exmc_fit_psis.hpp: z = (x - mu) / sigma, t = 0.5 * (z * z) + ls,
+// -(group_sum_slots(t, 0.0)) - log_norm, ls = exmc_log(sigma)
+template <int G, int DPL, int D>
+__device__ __forceinline__ double smc_base_logq(const double (&x)[DPL], const double (&mu)[DPL],
+                                                const double (&sg)[DPL], const double (&ls)[DPL],
+                                                const bool (&valid)[DPL], int l, double log_norm) {
+  double t[DPL];
+#pragma unroll
+  for (int k = 0; k < DPL; k++) {
+    const double z = (x[k] - mu[k]) / sg[k];
+    t[k] = 0.5 * (z * z) + ls[k];
+  }
+  return -group_sum_slots<G, DPL, D>(t, valid, l, 0.0) - log_norm;
+}
+
 __device__ __forceinline__ uint64_t smc_run_seed(const SmcParams& P, int run) {
   return P.base_seed + 7919ULL * (uint64_t)(P.run_lo + run);
 }
 
-// smc.ex:46-56 and :32-36; the first particle of a run also sets the run's state
-template <class M, int G>
-__global__ void __launch_bounds__(64) smc_init_kernel(SmcParams P, typename M::Consts mc) {
+// smc.ex:46-56 and :32-36; the first particle of a run also sets the run's state. kBridge: the start is the
+// base, q = mu + sigma * v, and lb and the evidence are set beside lp and the histories.
+template <class M, int G, bool kBridge>
+__device__ __forceinline__ void smc_init_body(const SmcParams& P, const SmcBridge& B, const typename M::Consts& mc) {
   constexpr int D = M::D, DPL = M::DPL;
   extern __shared__ double xlds[];
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -113,11 +146,30 @@ __global__ void __launch_bounds__(64) smc_init_kernel(SmcParams P, typename M::C
     rank[k] = valid[k] ? (P.flat.rank ? P.flat.rank[i] : i) : D;
     q[k] = g[k] = 0.0;
   }
-  for (int r = 0; r < D; r++) {
-    const double v = rng_normal(rng, zt, P.rng.nor_r) * 0.5;   // :50-51
+  double lb = 0.0;
+  if constexpr (kBridge) {
+    double mu[DPL], sg[DPL], ls[DPL];
 #pragma unroll
-    for (int k = 0; k < DPL; k++)
-      if (rank[k] == r) q[k] = v;
+    for (int k = 0; k < DPL; k++) {
+      const int i = l + k * G;
+      mu[k] = (valid[k] && B.mu) ? B.mu[i] : 0.0;
+      sg[k] = valid[k] ? (B.sigma ? B.sigma[i] : 0.5) : 1.0;
+      ls[k] = exmc_log(sg[k]);
+    }
+    for (int r = 0; r < D; r++) {
+      const double v = rng_normal(rng, zt, P.rng.nor_r);
+#pragma unroll
+      for (int k = 0; k < DPL; k++)
+        if (rank[k] == r) q[k] = mu[k] + sg[k] * v;
+    }
+    lb = smc_base_logq<G, DPL, D>(q, mu, sg, ls, valid, l, B.log_norm);
+  } else {
+    for (int r = 0; r < D; r++) {
+      const double v = rng_normal(rng, zt, P.rng.nor_r) * 0.5;   // :50-51
+#pragma unroll
+      for (int k = 0; k < DPL; k++)
+        if (rank[k] == r) q[k] = v;
+    }
   }
   const double raw = M::logp_grad(mc, ln, l, q, g);
   const double lp = exmc_isfinite(raw) ? raw : kSmcNonFinite;   // :35
@@ -127,6 +179,7 @@ __global__ void __launch_bounds__(64) smc_init_kernel(SmcParams P, typename M::C
     if (valid[k]) P.q[(size_t)(l + k * G) * C + chain] = q[k];
   if (l != 0) return;
   P.logp[chain] = lp;
+  if constexpr (kBridge) B.logb[chain] = lb;
   P.words[chain] = rng.a;
   P.words[(size_t)C + chain] = rng.b;
   P.runs.accept[chain] = 0;
@@ -139,18 +192,32 @@ __global__ void __launch_bounds__(64) smc_init_kernel(SmcParams P, typename M::C
   P.runs.active[run] = 1;
   P.runs.num_stages[run] = 0;
   P.runs.status[run] = 1;
+  if constexpr (kBridge) B.log_evidence[run] = 0.0;
   const double nan = exmc_from_bits(EXMC_NAN_BITS);
   for (int s = 0; s < P.max_stages; s++) {
     const size_t o = (size_t)s * R + run;
     P.runs.betas[o] = nan;
     P.runs.ess_history[o] = nan;
     P.runs.acceptance_rates[o] = nan;
+    if constexpr (kBridge) B.log_evidence_steps[o] = nan;
   }
 }
 
-// smc.ex:209-247 for one stage: the particle stays in registers across the num_mh_steps proposals
 template <class M, int G>
-__global__ void __launch_bounds__(64) smc_mutate_kernel(SmcParams P, typename M::Consts mc) {
+__global__ void __launch_bounds__(64) smc_init_kernel(SmcParams P, typename M::Consts mc) {
+  smc_init_body<M, G, false>(P, SmcBridge{}, mc);
+}
+
+template <class M, int G>
+__global__ void __launch_bounds__(64) smc_bridge_init_kernel(SmcParams P, SmcBridge B, typename M::Consts mc) {
+  smc_init_body<M, G, true>(P, B, mc);
+}
+
+// smc.ex:209-247 for one stage: the particle stays in registers across the num_mh_steps proposals. kBridge:
+// lb stays there too, lb' is one group_sum_slots per proposal, and the proposal is judged on the bridge:
+// log_alpha = (beta lp' + (1 - beta) lb') - (beta lp + (1 - beta) lb); a NaN log_alpha rejects.
+template <class M, int G, bool kBridge>
+__device__ __forceinline__ void smc_mutate_body(const SmcParams& P, const SmcBridge& B, const typename M::Consts& mc) {
   constexpr int D = M::D, DPL = M::DPL;
   extern __shared__ double xlds[];
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -182,6 +249,18 @@ __global__ void __launch_bounds__(64) smc_mutate_kernel(SmcParams P, typename M:
   Rng rng{P.words[chain], P.words[(size_t)C + chain]};
   const double beta = P.runs.beta[run];
   int accepted = 0;
+  double lb = 0.0, omb = 0.0, mu[kBridge ? DPL : 1], sg[kBridge ? DPL : 1], ls[kBridge ? DPL : 1];
+  if constexpr (kBridge) {
+#pragma unroll
+    for (int k = 0; k < DPL; k++) {
+      const int i = l + k * G;
+      mu[k] = (valid[k] && B.mu) ? B.mu[i] : 0.0;
+      sg[k] = valid[k] ? (B.sigma ? B.sigma[i] : 0.5) : 1.0;
+      ls[k] = exmc_log(sg[k]);
+    }
+    lb = B.logb[chain];
+    omb = 1.0 - beta;
+  }
 
   for (int s = 0; s < P.num_mh_steps; s++) {
     double prop[DPL], g[DPL];
@@ -200,15 +279,24 @@ __global__ void __launch_bounds__(64) smc_mutate_kernel(SmcParams P, typename M:
     }
     const double raw = M::logp_grad(mc, ln, l, prop, g);
     const double lpp = exmc_isfinite(raw) ? raw : kSmcNonFinite;   // :223
-    const double log_alpha = beta * (lpp - lp);                    // :227
+    double log_alpha, lbp = 0.0;
+    if constexpr (kBridge) {
+      lbp = smc_base_logq<G, DPL, D>(prop, mu, sg, ls, valid, l, B.log_norm);
+      const double tc = beta * lp + omb * lb, tp = beta * lpp + omb * lbp;
+      log_alpha = tp - tc;
+    } else {
+      log_alpha = beta * (lpp - lp);                               // :227
+    }
     bool take = false;
     if (active) {
       const double u = rng_uniform(rng);                           // :232
       take = (u == 0.0) || (exmc_log(u) < log_alpha);              // :234; u = 0: a stated deviation
+      if constexpr (kBridge) take = take && (log_alpha == log_alpha);
     }
 #pragma unroll
     for (int k = 0; k < DPL; k++) q[k] = take ? prop[k] : q[k];
     lp = take ? lpp : lp;
+    if constexpr (kBridge) lb = take ? lbp : lb;
     accepted += take ? 1 : 0;
   }
 
@@ -218,9 +306,20 @@ __global__ void __launch_bounds__(64) smc_mutate_kernel(SmcParams P, typename M:
     if (valid[k]) P.q[(size_t)(l + k * G) * C + chain] = q[k];
   if (l != 0) return;
   P.logp[chain] = lp;
+  if constexpr (kBridge) B.logb[chain] = lb;
   P.words[chain] = rng.a;
   P.words[(size_t)C + chain] = rng.b;
   P.runs.accept[chain] = accepted;
+}
+
+template <class M, int G>
+__global__ void __launch_bounds__(64) smc_mutate_kernel(SmcParams P, typename M::Consts mc) {
+  smc_mutate_body<M, G, false>(P, SmcBridge{}, mc);
+}
+
+template <class M, int G>
+__global__ void __launch_bounds__(64) smc_bridge_mutate_kernel(SmcParams P, SmcBridge B, typename M::Consts mc) {
+  smc_mutate_body<M, G, true>(P, B, mc);
 }
 
 #ifndef EXMC_ONLY_CUSTOM   // a generated model's plug-in carries no model-free kernels
@@ -303,9 +402,13 @@ __global__ __launch_bounds__(kSmcBlock) void smc_close_kernel(SmcStage S) {
 
 // One workgroup per run: the bisection (:147-178), the stage's weights and ESS (:107-117). nw [R][N];
 // resample [R] = 1 where ess < threshold (:120). kLds: the run's logps stay in LDS.
-template <bool kLds>
-__global__ __launch_bounds__(kSmcBlock) void smc_weights_kernel(SmcStage S, const double* __restrict__ logp,
-                                                               double* __restrict__ nw, int32_t* __restrict__ resample) {
+// kBridge (DESIGN.md "Bridged SMC" 3-5): the weights are of lr_j = lp_j - lb_j; the stage's first evaluation
+// is at 1.0 - beta and ends the temper when its ESS is at or above the threshold, otherwise the bisection
+// runs as it is; inc = mx + log(sw / N) is the stage's share of the log evidence; every stage resamples.
+template <bool kLds, bool kBridge>
+__device__ __forceinline__ void smc_weights_body(const SmcStage& S, const double* __restrict__ logp,
+                                                 const SmcBridge& B, double* __restrict__ nw,
+                                                 int32_t* __restrict__ resample) {
   extern __shared__ double lds_lp[];
   __shared__ double red[kSmcBlock / 64];
   const int tid = threadIdx.x, r = blockIdx.x, N = S.n_particles, R = S.n_runs;
@@ -314,24 +417,32 @@ __global__ __launch_bounds__(kSmcBlock) void smc_weights_kernel(SmcStage S, cons
     return;
   }
   const double* lp = logp + (size_t)r * N;
+  const double* lb = kBridge ? B.logb + (size_t)r * N : nullptr;
   if (kLds) {
-    for (int j = tid; j < N; j += kSmcBlock) lds_lp[j] = lp[j];
+    for (int j = tid; j < N; j += kSmcBlock) lds_lp[j] = kBridge ? lp[j] - lb[j] : lp[j];
     __syncthreads();
     lp = lds_lp;
   }
+  auto at = [&](int j) { return (kBridge && !kLds) ? lp[j] - lb[j] : lp[j]; };
   const double beta = S.runs.beta[r], thr = S.threshold;
   double mx = 0.0, sw = 1.0;
   auto ess_at = [&](double delta) {
-    mx = particle_max(N, tid, red, [&](int j) { return delta * lp[j]; });
-    sw = particle_sum(N, tid, red, [&](int j) { return exmc_exp(delta * lp[j] - mx); });
+    mx = particle_max(N, tid, red, [&](int j) { return delta * at(j); });
+    sw = particle_sum(N, tid, red, [&](int j) { return exmc_exp(delta * at(j) - mx); });
     const double s2 = particle_sum(N, tid, red, [&](int j) {
-      const double w = exmc_exp(delta * lp[j] - mx) / sw;
+      const double w = exmc_exp(delta * at(j) - mx) / sw;
       return w * w;
     });
     return 1.0 / s2;
   };
   double lo = beta, hi = 1.0, next = 0.0;
   bool found = false;
+  if constexpr (kBridge) {
+    if (ess_at(1.0 - beta) >= thr) {   // block-uniform
+      next = 1.0;
+      found = true;
+    }
+  }
   for (int it = 0; it < kSmcBisect && !found; it++) {   // block-uniform: every lane holds the same sums
     const double mid = (lo + hi) / 2.0;
     const double ess = ess_at(mid - beta);
@@ -348,14 +459,32 @@ __global__ __launch_bounds__(kSmcBlock) void smc_weights_kernel(SmcStage S, cons
   const double new_beta = fmin(next, 1.0);   // :104
   const double ess = ess_at(new_beta - beta);
   const double delta = new_beta - beta;
-  for (int j = tid; j < N; j += kSmcBlock) nw[(size_t)r * N + j] = exmc_exp(delta * lp[j] - mx) / sw;
+  for (int j = tid; j < N; j += kSmcBlock) nw[(size_t)r * N + j] = exmc_exp(delta * at(j) - mx) / sw;
   if (tid == 0) {
-    resample[r] = (ess < thr) ? 1 : 0;
+    resample[r] = (kBridge || ess < thr) ? 1 : 0;
     S.runs.beta[r] = new_beta;
     S.runs.betas[(size_t)S.stage * R + r] = new_beta;
     S.runs.ess_history[(size_t)S.stage * R + r] = ess;
     S.runs.num_stages[r] = S.stage + 1;
+    if constexpr (kBridge) {
+      const double inc = mx + exmc_log(sw / (double)N);
+      B.log_evidence_steps[(size_t)S.stage * R + r] = inc;
+      B.log_evidence[r] = B.log_evidence[r] + inc;
+    }
   }
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kSmcBlock) void smc_weights_kernel(SmcStage S, const double* __restrict__ logp,
+                                                               double* __restrict__ nw, int32_t* __restrict__ resample) {
+  smc_weights_body<kLds, false>(S, logp, SmcBridge{}, nw, resample);
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kSmcBlock) void smc_bridge_weights_kernel(SmcStage S, const double* __restrict__ logp,
+                                                                      SmcBridge B, double* __restrict__ nw,
+                                                                      int32_t* __restrict__ resample) {
+  smc_weights_body<kLds, true>(S, logp, B, nw, resample);
 }
 
 // One workgroup per run (:180-195) over the cumulative sums of ratio_scan_kernel (linear, S = 1, Nb = R,
@@ -387,16 +516,20 @@ __global__ __launch_bounds__(kSmcBlock) void smc_resample_kernel(SmcStage S, con
   }
 }
 
-// rows 0 .. d - 1 of q [d][C] and, as row d, logp [C], gathered by idx inside every run (:192-193)
+// rows 0 .. d - 1 of q [d][C] and, as row d, logp [C], gathered by idx inside every run (:192-193); in the
+// bridged mode logb [C] travels as row d + 1 (null otherwise)
 __global__ __launch_bounds__(256) void smc_gather_kernel(const double* __restrict__ q, const double* __restrict__ logp,
+                                                        const double* __restrict__ logb,
                                                         const int32_t* __restrict__ idx, int d, int N, long long C,
-                                                        double* __restrict__ q2, double* __restrict__ logp2) {
+                                                        double* __restrict__ q2, double* __restrict__ logp2,
+                                                        double* __restrict__ logb2) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= ((long long)d + 1) * C) return;
+  if (e >= ((long long)d + (logb ? 2 : 1)) * C) return;
   const long long row = e / C, c = e - row * C;
   const long long src = (c / N) * N + idx[c];
   if (row < d) q2[e] = q[row * C + src];
-  else logp2[c] = logp[src];
+  else if (row == d) logp2[c] = logp[src];
+  else logb2[c] = logb[src];
 }
 
 // One workgroup per (run, dimension): estimate_scale (:197-207)
